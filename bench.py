@@ -33,10 +33,18 @@ stand-in step, no measurement): the multi-rank CPU test uses it.
 Timing: barrier + synchronize around exactly --steps steps, max over ranks.
 
 Also reported: the roofline of the kernel (algorithmic bytes per launch /
-average launch time from HIP events on the launch stream, vs 8 TB/s) and the
+average launch time from HIP events on the launch stream, vs 8 TB/s).
+
+A plain run does only what the headline figure needs: set up, warm up, time
+the steps, print the line.  --full adds what takes runs of its own: the
 reference's own CPU path (oracle/_ref, compiled from the reference sources;
 the C restatement when that is absent) timed on a bounded sample on rank 0,
-on 1 thread and batch-parallel on up to 16 threads.
+on 1 thread and batch-parallel on up to 16 threads ("cpu_baseline", null
+without --full), and at world > 1 with a step of more than the one launch
+(cfg5) the launch's own event timing ("roofline", null there without --full)
+and "global_stats_check".  --dump-outputs DIR writes what the last timed step
+computed (rank 0's batch) as DIR/<name>.npy; the inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -74,7 +82,53 @@ def parse():
                     help="replay the step from a captured HIP graph (measured no faster than eager launches)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / rank-protocol check on CPU: gloo, a CPU stand-in step, no GPU, no measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baseline, and at world > 1 "
+                         "the dominant kernel's own timing (roofline) and the global-statistics check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step computed as DIR/<name>.npy "
+                         "(float32 / float64; a fixed seeded sample of arrays over the size cap)")
     return ap.parse_args()
+
+
+# --dump-outputs: an array of more elements than this is written as a fixed
+# seeded sample of its flattened values (12 Mi fp32 = 48 MiB; with cfg5's
+# statistics, a few hundred bytes, the directory stays under 64 MB)
+DUMP_MAX_ELEMS = 12 * 1024 * 1024
+DUMP_SEED = 20240607
+
+
+def dump_outputs(directory: str, outputs: dict) -> None:
+    """Write the arrays a caller of the timed path receives (rank 0's own
+    batch) as DIR/<name>.npy: floating arrays in their own precision, integer
+    ones (u8 frames) as float32, which holds them exactly.  The sample's
+    indices depend only on the array's size and DUMP_SEED, so two builds run
+    with the same arguments write comparable files; manifest.json names the
+    full shape and the sampling of each."""
+    import numpy as np
+    import torch
+    d = Path(directory)
+    d.mkdir(parents=True, exist_ok=True)
+    manifest = {}
+    for name, t in outputs.items():
+        t = t.detach()
+        n = t.numel()
+        flat = t.reshape(-1)
+        sampled = n > DUMP_MAX_ELEMS
+        if sampled:
+            idx = np.random.default_rng(DUMP_SEED).integers(0, n, size=DUMP_MAX_ELEMS, dtype=np.int64)
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        a = flat.cpu().numpy()
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+        if not sampled:
+            a = a.reshape(tuple(t.shape))
+        np.save(d / f"{name}.npy", a)
+        manifest[name] = {"shape": list(t.shape), "source_dtype": str(t.dtype).replace("torch.", ""),
+                          "saved_dtype": str(a.dtype), "saved_elements": int(a.size),
+                          "sample": ({"of": "flattened array", "seed": DUMP_SEED,
+                                      "draw": "numpy default_rng(seed).integers(0, numel, saved_elements)"}
+                                     if sampled else None)}
+    (d / "manifest.json").write_text(json.dumps(manifest, indent=1) + "\n")
 
 
 def spawn_ranks(n: int) -> int:
@@ -290,7 +344,8 @@ def make_workload(name: str, batch: int, dev, rank: int, world: int, ops) -> dic
         return {"batch": B, "px": 1280 * 720, "b_alg": B * 2 * 1280 * 720 * 3, "kernel": "warp_exp_kernel",
                 "frame": "1280x720x3", "output": "1280x720x3 u8",
                 "desc": "warp_affine INTER_LINEAR BORDER_CONSTANT 1280x720x3 u8, scale 0.9 rot 15 aux (640,360,640,360)",
-                "main": lambda stream=None: ops.warp_affine(src, m, 1280, 720, out=dst, stream=stream)}
+                "main": lambda stream=None: ops.warp_affine(src, m, 1280, 720, out=dst, stream=stream),
+                "outputs": lambda: {"output": dst}}
     if name == "cvt_normalize":
         B = batch or 256
         yuv = u8(B, 1620, 1920)
@@ -298,7 +353,8 @@ def make_workload(name: str, batch: int, dev, rank: int, world: int, ops) -> dic
         return {"batch": B, "px": 1920 * 1080, "b_alg": B * (1920 * 1620 + 1920 * 1080 * 12), "kernel": "color_kernel",
                 "frame": "NV21 1920x1620", "output": "1920x1080x3 fp32",
                 "desc": "cvt_color YUV2BGR_NV21 1080p + normalize(mean/std) -> 1920x1080x3 fp32, one pass",
-                "main": lambda stream=None: ops.cvt_color_normalize(yuv, mean=MEAN, std=STD, out=dst, stream=stream)}
+                "main": lambda stream=None: ops.cvt_color_normalize(yuv, mean=MEAN, std=STD, out=dst, stream=stream),
+                "outputs": lambda: {"output": dst}}
     if name == "yuv_resize":
         B = batch or 256
         yuv = u8(B, 1620, 1920)
@@ -307,7 +363,8 @@ def make_workload(name: str, batch: int, dev, rank: int, world: int, ops) -> dic
                 "kernel": "yuv_cols_kernel", "frame": "NV21 1920x1620", "output": "3x360x640 fp32 (NCHW)",
                 "desc": "cvt_color NV21 -> resize INTER_LINEAR 640x360 -> normalize -> NCHW, one kernel",
                 "main": lambda stream=None: ops.cvt_color_resize_normalize(yuv, 640, 360, MEAN, STD, out=dst,
-                                                                           stream=stream)}
+                                                                           stream=stream),
+                "outputs": lambda: {"output": dst}}
     if name == "cubic_stats":
         from vacv_amd import INTER_CUBIC
         B = batch or 128
@@ -339,7 +396,8 @@ def make_workload(name: str, batch: int, dev, rank: int, world: int, ops) -> dic
         return {"batch": B, "px": 2560 * 1440, "b_alg": B * resize_bytes(2560, 1440, 3, 224, 224, 1, 4, cubic=True),
                 "kernel": "cubic_cols_kernel", "frame": "2560x1440x3", "output": "224x224x3 fp32 + global mean/std",
                 "desc": "resize INTER_CUBIC 2560x1440x3 u8 -> 224x224x3 fp32 + global mean_stddev (RCCL all-reduce)",
-                "main": main, "extra": extra, "stats": stats, "inputs": src}
+                "main": main, "extra": extra, "stats": stats, "inputs": src,
+                "outputs": lambda: {"output": dst, "sums": stats["sums"], "mean": stats["mean"], "std": stats["std"]}}
     if name == "resize_normalize_720p":
         B = batch or 256
         src = u8(B, H_IN, W_IN, C)
@@ -348,7 +406,8 @@ def make_workload(name: str, batch: int, dev, rank: int, world: int, ops) -> dic
                 "kernel": "resize_strip_kernel", "frame": "1920x1080x3", "output": "1280x720x3 fp32",
                 "desc": "resize_normalize INTER_LINEAR 1920x1080x3 u8 NHWC -> 1280x720x3 fp32 "
                         "(reference arithmetic, two weighted source rows per output row) + per-channel normalize",
-                "main": lambda stream=None: ops.resize_normalize(src, 1280, 720, MEAN, STD, out=dst, stream=stream)}
+                "main": lambda stream=None: ops.resize_normalize(src, 1280, 720, MEAN, STD, out=dst, stream=stream),
+                "outputs": lambda: {"output": dst}}
     B = batch or 256
     src = u8(B, H_IN, W_IN, C)
     dst = torch.empty((B, H_OUT, W_OUT, C), dtype=torch.float32, device=dev)
@@ -356,7 +415,8 @@ def make_workload(name: str, batch: int, dev, rank: int, world: int, ops) -> dic
             "kernel": "resize_cols_kernel", "frame": "1920x1080x3", "output": "640x360x3 fp32",
             "desc": "resize_normalize INTER_LINEAR 1920x1080x3 u8 NHWC -> 640x360x3 fp32 "
                     "(reference arithmetic) + per-channel normalize",
-            "main": lambda stream=None: ops.resize_normalize(src, W_OUT, H_OUT, MEAN, STD, out=dst, stream=stream)}
+            "main": lambda stream=None: ops.resize_normalize(src, W_OUT, H_OUT, MEAN, STD, out=dst, stream=stream),
+            "outputs": lambda: {"output": dst}}
 
 
 def dry_run(args, world: int, rank: int) -> None:
@@ -518,6 +578,8 @@ def main():
     # the statistics the last timed step produced (the kernel-only re-timing
     # below overwrites the workload's buffers with per-rank sums)
     step_sums = wl["stats"]["sums"].clone() if (extra and "stats" in wl) else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, wl["outputs"]())  # the last timed step's, before anything else launches
 
     # The dominant kernel's average duration (roofline): the timed region's
     # GPU time / K, from that one HIP event pair on the launch stream, where a
@@ -527,9 +589,12 @@ def main():
     # between two launches idled the GPU ~8-10 us (rocprofv3 kernel trace:
     # back-to-back cfg5 launches 0 us apart, 10 us apart with events), ~5 % of
     # a step.  With an extra (multi-GPU cfg5: the all-reduce), the main launch
-    # alone is timed again, K times, each bracketed by events.
+    # alone is timed again, K times, each bracketed by events: a run of its
+    # own, so only under --full (a plain run then reports no roofline).
     if extra is None:
         kern_ms = gpu_step_ms
+    elif not args.full:
+        kern_ms = None
     else:
         ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
         for i in range(args.steps):
@@ -541,9 +606,9 @@ def main():
 
     # cfg5 across ranks: the step's statistics must be the GLOBAL ones -- the
     # all-reduced sums equal the sum of every rank's own shard sums (recomputed
-    # here, gathered to the host, added in rank order)
+    # here, gathered to the host, added in rank order; under --full)
     stats_check = None
-    if world > 1 and step_sums is not None:
+    if args.full and world > 1 and step_sums is not None:
         import numpy as np
         from vacv_amd import INTER_CUBIC
         mine = ops.resize_channel_sums(wl["inputs"], 224, 224, INTER_CUBIC, per_image=False)[1].cpu().numpy()
@@ -557,22 +622,29 @@ def main():
             print(f"bench: global statistics differ from the ranks' sums (rel {rel:g})", file=sys.stderr)
             sys.exit(3)
 
-    t = torch.tensor([elapsed, kern_ms], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
+    t = torch.tensor([elapsed, kern_ms or 0.0], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-    elapsed, kern_ms = float(t[0]), float(t[1])
+    elapsed = float(t[0])
+    kern_ms = float(t[1]) if kern_ms is not None else None
     ms_per_step = elapsed * 1e3 / args.steps
 
     n_img = B * world
     value = n_img * wl["px"] / (ms_per_step / 1e3) / 1e6
     b_alg = wl["b_alg"]  # per launch (one GPU's batch)
-    achieved = b_alg / (kern_ms / 1e3) / 1e9
-    traffic = pmc_traffic(args.workload)
+    roofline = None
+    if kern_ms is not None:
+        achieved = b_alg / (kern_ms / 1e3) / 1e9
+        roofline = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": pmc_traffic(args.workload),
+                    "kernel": wl["kernel"], "kernel_ms": round(kern_ms, 4), "alg_bytes_per_launch": b_alg,
+                    "gpu_ms_per_step": round(gpu_step_ms, 4)}
 
     out = None
     if rank == 0:
-        # the host-CPU leg runs at N = 1 only (the multi-GPU lines time the GPUs)
-        cpu = None if (args.no_cpu_baseline or world > 1) else cpu_baseline(args.cpu_seconds, args.workload)
+        # the host-CPU leg: under --full, at N = 1 only (the multi-GPU lines time the GPUs)
+        cpu = (cpu_baseline(args.cpu_seconds, args.workload)
+               if (args.full and not args.no_cpu_baseline and world == 1) else None)
         out = {
             "metric": "Mpixels/sec per op (resize/warp/normalize) at 1080p; achieved HBM GB/s vs peak",
             "value": round(value, 2),
@@ -589,10 +661,7 @@ def main():
             "config": {"workload": wl["desc"], "global_batch": n_img, "batch_per_gpu": B,
                        "parallelism": f"dp{world}", "frame": wl["frame"], "output": wl["output"],
                        "graph": graph is not None, "backend": backend if world > 1 else None},
-            "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
-                         "kernel": wl["kernel"], "kernel_ms": round(kern_ms, 4), "alg_bytes_per_launch": b_alg,
-                         "gpu_ms_per_step": round(gpu_step_ms, 4)},
+            "roofline": roofline,
             "cpu_baseline": cpu,
         }
         if stats_check is not None:

@@ -38,9 +38,22 @@ def build_oracle() -> None:
     subprocess.run(["make", "-s", "-C", str(HERE), "oracle"], check=True)
 
 
+def reference_sources() -> Path | None:
+    """The reference's src/ directory that oracle/Makefile compiles from (its
+    REF default, or $REF as make itself takes it), or None where it is absent
+    or this user may not read it."""
+    import re
+    m = re.search(r"^REF[ \t]*\?=[ \t]*(\S+)", (HERE / "Makefile").read_text(), re.M)
+    src = Path(os.environ.get("REF") or m.group(1))
+    try:
+        return src if (src / "cv" / "resize_naive.cpp").exists() else None
+    except OSError:  # a parent directory this user may not enter: as good as absent
+        return None
+
+
 def build_reference() -> bool:
     """Build oracle/_ref when the reference sources are present."""
-    if not Path("/root/reference/src/cv/resize_naive.cpp").exists():
+    if reference_sources() is None:
         return REF_SO.exists()
     subprocess.run(["make", "-s", "-C", str(HERE), "ref"], check=True)
     return True

@@ -36,6 +36,48 @@ def test_workload_choices_match_parser(monkeypatch):
         assert bench.parse().workload == w
 
 
+def test_plain_run_is_the_default(monkeypatch):
+    """--full and --dump-outputs are off unless asked for."""
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "somewhere"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "somewhere"
+
+
+def test_dump_outputs_files(monkeypatch, tmp_path):
+    """dump_outputs on host tensors: small arrays whole and in shape, u8 as
+    float32 (exact), float64 kept; an array over the cap as a sample of its
+    flattened values whose indices depend on its size and the seed alone."""
+    import json
+
+    import numpy as np
+    import torch
+
+    import bench
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMS", 1000)
+    big = torch.arange(5000, dtype=torch.float32).reshape(50, 100) * 0.5
+    frames = torch.arange(2 * 3 * 4 * 3, dtype=torch.int64).reshape(2, 3, 4, 3).to(torch.uint8)
+    sums = torch.tensor([[1.0, 2.0], [3.0, 1e300]], dtype=torch.float64)
+    for sub in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / sub), {"output": big, "frames": frames, "sums": sums})
+    a = tmp_path / "a"
+    got = np.load(a / "frames.npy")
+    assert got.dtype == np.float32 and got.shape == (2, 3, 4, 3) and np.array_equal(got, frames.numpy())
+    got = np.load(a / "sums.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, sums.numpy())
+    got = np.load(a / "output.npy")
+    idx = np.random.default_rng(bench.DUMP_SEED).integers(0, 5000, size=1000, dtype=np.int64)
+    assert got.dtype == np.float32 and got.shape == (1000,) and np.array_equal(got, big.numpy().reshape(-1)[idx])
+    assert np.array_equal(got, np.load(tmp_path / "b" / "output.npy"))
+    m = json.loads((a / "manifest.json").read_text())
+    assert m["output"]["shape"] == [50, 100] and m["output"]["sample"]["seed"] == bench.DUMP_SEED
+    assert m["frames"]["sample"] is None and m["frames"]["source_dtype"] == "uint8"
+    assert sorted(p.name for p in a.iterdir()) == ["frames.npy", "manifest.json", "output.npy", "sums.npy"]
+
+
 def _run_bench(args, env_extra=None, timeout=240):
     import json
     import os
@@ -78,11 +120,12 @@ def test_bench_main_two_ranks_on_one_gpu(workload):
     the shard-size check, cfg5's all-reduce and the MAX-over-ranks merge --
     with two ranks on the box's one GPU: VACV_BENCH_BACKEND=gloo replaces RCCL
     (which needs a GPU per rank).  The parent spawns the ranks before anything
-    touches the GPU.  One JSON line, n_gpus 2, dp2, a roofline and a finite
+    touches the GPU.  --full: the kernel's own timing (roofline) and the
+    global-statistics check are not part of a plain run.  One JSON line, n_gpus 2, dp2, a roofline and a finite
     step time; cfg5's statistics are global (the count covers both shards)."""
     import math
     rc, lines, err = _run_bench(["--gpus", "2", "--workload", workload, "--steps", "3", "--warmup", "1",
-                                 "--no-cpu-baseline"], {"VACV_BENCH_BACKEND": "gloo"}, timeout=300)
+                                 "--full", "--no-cpu-baseline"], {"VACV_BENCH_BACKEND": "gloo"}, timeout=300)
     assert rc == 0, err[-3000:]
     assert len(lines) == 1, lines
     out = lines[0]
@@ -94,6 +137,39 @@ def test_bench_main_two_ranks_on_one_gpu(workload):
     assert out["value"] > 0 and out["cpu_baseline"] is None
     if workload == "cubic_stats":
         assert out["global_stats_check"]["ok"], out["global_stats_check"]
+
+
+@pytest.mark.gpu
+def test_plain_run_dumps_last_step_outputs(hip_device, tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` run: the headline line
+    with ms_per_step for exactly K steps and a roofline, no CPU baseline (that
+    is --full's), and --dump-outputs holding what the step computed -- bit for
+    bit what the same seeded workload gives in this process."""
+    import math
+
+    import numpy as np
+    import torch
+    rc, lines, err = _run_bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "2",
+                                 "--dump-outputs", str(tmp_path / "dump")], timeout=120)
+    assert rc == 0, err[-3000:]
+    assert len(lines) == 1, lines
+    out = lines[0]
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["n_gpus"] == 1
+    assert out["unit"] == "Mpixels/s" and out["higher_is_better"] is True and out["dtype"] == "u8"
+    assert math.isfinite(out["ms_per_step"]) and out["ms_per_step"] > 0
+    # value = frames' pixels / step time; the line rounds ms_per_step to 1e-4 ms and value to 0.01
+    want = 2 * 1920 * 1080 / (out["ms_per_step"] / 1e3) / 1e6
+    assert abs(out["value"] - want) <= want * 0.5e-4 / (out["ms_per_step"] - 0.5e-4) + 0.01
+    assert out["cpu_baseline"] is None and out["roofline"]["kernel_ms"] > 0
+    got = np.load(tmp_path / "dump" / "output.npy")
+    assert got.dtype == np.float32 and got.shape == (2, 360, 640, 3)
+
+    import bench
+    from vacv_amd import ops
+    wl = bench.make_workload("resize_normalize", 2, hip_device, 0, 1, ops)
+    wl["main"]()
+    torch.cuda.synchronize()
+    assert np.array_equal(got, wl["outputs"]()["output"].cpu().numpy())
 
 
 def test_gpus_8_dry_run_single_line():
