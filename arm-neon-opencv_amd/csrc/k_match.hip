@@ -415,7 +415,9 @@ __global__ void __launch_bounds__(kBlock) match_vsum_u8_kernel(MatchLaunch M) {
     }
 }
 
-// grid (rh, n); dynamic LDS 2 (iw + 1) cn uint32
+// grid (rh, n); dynamic LDS 2 (iw + 1) cn uint32, next to the static per-wave
+// totals: the launcher's 64 KiB budget counts both
+using MatchFinishWaveTotals = uint32_t[2][4][kBlock / 64];
 __global__ void __launch_bounds__(kBlock) match_finish_u8_kernel(MatchLaunch M) {
     extern __shared__ __attribute__((aligned(16))) uint32_t pre[];
     const int cn = M.cn, E = M.iw * cn, PE = E + cn;  // prefix row: cn leading zeros
@@ -449,7 +451,7 @@ __global__ void __launch_bounds__(kBlock) match_finish_u8_kernel(MatchLaunch M) 
         }
     }
     // exclusive scan of the thread totals over the workgroup, per channel
-    __shared__ uint32_t wtot[2][4][kBlock / 64];
+    __shared__ MatchFinishWaveTotals wtot;
     uint32_t xs[4], xq[4];
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
@@ -894,7 +896,9 @@ hipError_t launch_match_template(const MatchLaunch& M, hipStream_t s) {
     if (e != hipSuccess || M.method == VACV_TM_CCORR) return e;
     if (M.esize == 1) hipLaunchKernelGGL(match_tstats_kernel<uint8_t>, dim3(1), dim3(kBlock), 0, s, M);
     else hipLaunchKernelGGL(match_tstats_kernel<float>, dim3(1), dim3(kBlock), 0, s, M);
-    if (M.esize == 1 && (int64_t)M.tw * M.th <= 66000 && 2 * (int64_t)(M.iw + 1) * M.cn * 4 <= 64 * 1024) {
+    // match_finish_u8_kernel's LDS: the dynamic prefix rows plus its static wave totals
+    const int64_t finish_lds = 2 * (int64_t)(M.iw + 1) * M.cn * 4 + (int64_t)sizeof(MatchFinishWaveTotals);
+    if (M.esize == 1 && (int64_t)M.tw * M.th <= 66000 && finish_lds <= 64 * 1024) {
         // u8: exact integer box sums (the same values as the integrals)
         const int E = M.iw * M.cn;
         const dim3 gv((E + kBlock - 1) / kBlock, (M.rh + kVsRows - 1) / kVsRows, M.n);

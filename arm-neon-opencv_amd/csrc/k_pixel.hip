@@ -119,19 +119,32 @@ __global__ void __launch_bounds__(kBlock) chw_to_hwc3_u8_kernel(LayoutLaunch L) 
 
 // --------------------------------------------------------------------------
 // u8 <-> f32 over a dense buffer (tensor.cpp:459-502).
+// u8_to_f32_kernel / f32_to_u8_kernel are the fallbacks for a base that
+// forbids the flat kernels' dword and 16-byte accesses (a view at an odd
+// offset into a larger allocation): one element per step, so every access is
+// as wide as its own type and naturally aligned -- any address for u8, the
+// 4-byte alignment an fp32 image always has for float.  The slow path.
 __global__ void __launch_bounds__(kBlock) u8_to_f32_kernel(DtypeLaunch L) {
-    const int64_t n16 = L.count >> 4;
-    for (int64_t i = gtid(); i < n16; i += gstride()) {
-        const uint4 v = reinterpret_cast<const uint4*>(L.src)[i];
-        float4* d = reinterpret_cast<float4*>(L.dst) + i * 4;
-        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            d[j] = make_float4((float)(w[j] & 0xFF), (float)((w[j] >> 8) & 0xFF), (float)((w[j] >> 16) & 0xFF),
-                               (float)(w[j] >> 24));
+    float* d = reinterpret_cast<float*>(L.dst);
+    for (int64_t i = gtid(); i < L.count; i += gstride()) d[i] = (float)L.src[i];
+}
+
+// u8 -> f32 between pitched images (the equal-size shortcut of an INTER_CUBIC
+// u8 -> fp32 vacv_resize on a non-dense pair): L.row_bytes u8 elements per
+// (image, plane, row), one element per step as above.
+__global__ void __launch_bounds__(kBlock) u8_to_f32_rows_kernel(CopyLaunch L) {
+    const int64_t rows_per_img = (int64_t)L.src.planes * L.src.h;
+    const int64_t total = rows_per_img * L.n * L.row_bytes;
+    for (int64_t e = gtid(); e < total; e += gstride()) {
+        const int64_t r = e / L.row_bytes, x = e - r * L.row_bytes;
+        const int64_t img = r / rows_per_img;
+        const int64_t rr = r - img * rows_per_img;
+        const int64_t plane = rr / L.src.h, y = rr - plane * L.src.h;
+        const unsigned char* s = L.src.base + img * L.src.img_pitch + plane * L.src.plane_pitch + y * L.src.row_pitch;
+        unsigned char* d = const_cast<unsigned char*>(L.dst.base) + img * L.dst.img_pitch +
+                           plane * L.dst.plane_pitch + y * L.dst.row_pitch;
+        reinterpret_cast<float*>(d)[x] = (float)s[x];
     }
-    for (int64_t i = (n16 << 4) + gtid(); i < L.count; i += gstride())
-        reinterpret_cast<float*>(L.dst)[i] = (float)L.src[i];
 }
 
 // One dword of u8 in, one 16-byte float4 out per thread over a grid that
@@ -169,20 +182,8 @@ __global__ void __launch_bounds__(kBlock) f32_to_u8_flat_kernel(DtypeLaunch L) {
 }
 
 __global__ void __launch_bounds__(kBlock) f32_to_u8_kernel(DtypeLaunch L) {
-    const int64_t n16 = L.count >> 4;
-    for (int64_t i = gtid(); i < n16; i += gstride()) {
-        const float4* s = reinterpret_cast<const float4*>(L.src) + i * 4;
-        uint32_t w[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float4 f = s[j];
-            w[j] = (uint32_t)f32_to_u8_neon(f.x) | ((uint32_t)f32_to_u8_neon(f.y) << 8) |
-                   ((uint32_t)f32_to_u8_neon(f.z) << 16) | ((uint32_t)f32_to_u8_neon(f.w) << 24);
-        }
-        reinterpret_cast<uint4*>(L.dst)[i] = make_uint4(w[0], w[1], w[2], w[3]);
-    }
-    for (int64_t i = (n16 << 4) + gtid(); i < L.count; i += gstride())
-        L.dst[i] = f32_to_u8_neon(reinterpret_cast<const float*>(L.src)[i]);
+    const float* f = reinterpret_cast<const float*>(L.src);
+    for (int64_t i = gtid(); i < L.count; i += gstride()) L.dst[i] = f32_to_u8_neon(f[i]);
 }
 
 // --------------------------------------------------------------------------
@@ -1602,9 +1603,19 @@ hipError_t launch_dtype(const DtypeLaunch& L, hipStream_t s) {
         else hipLaunchKernelGGL(f32_to_u8_flat_kernel, dim3(blocks), dim3(kBlock), 0, s, L);
         return hipGetLastError();
     }
-    const int g = grid_for(L.count / 16 + 1);
+    if ((a32 & 3) != 0) return hipErrorInvalidValue;  // no fp32 image starts off a float boundary
+    const int g = grid_for(L.count);
     if (L.to_f32) hipLaunchKernelGGL(u8_to_f32_kernel, dim3(g), dim3(kBlock), 0, s, L);
     else hipLaunchKernelGGL(f32_to_u8_kernel, dim3(g), dim3(kBlock), 0, s, L);
+    return hipGetLastError();
+}
+
+hipError_t launch_u8_to_f32_rows(const CopyLaunch& L, hipStream_t s) {
+    const uintptr_t bits = reinterpret_cast<uintptr_t>(L.dst.base) | (uintptr_t)L.dst.img_pitch |
+                           (uintptr_t)L.dst.plane_pitch | (uintptr_t)L.dst.row_pitch;
+    if ((bits & 3) != 0) return hipErrorInvalidValue;  // every fp32 row on a float boundary
+    const int g = grid_for((int64_t)L.src.planes * L.src.h * L.n * L.row_bytes);
+    hipLaunchKernelGGL(u8_to_f32_rows_kernel, dim3(g), dim3(kBlock), 0, s, L);
     return hipGetLastError();
 }
 

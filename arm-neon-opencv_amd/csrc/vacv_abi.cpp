@@ -783,8 +783,17 @@ int vacv_resize(const vacv_image* src_d, const vacv_image* dst_d, int interpolat
             const int cc = src.layout == VACV_NHWC ? src.c : 1;
             return copy_rows(src, dst, 0, src.h, (int64_t)src.w * cc * src.es, s);
         }
-        if (src.dtype == VACV_INT8 && dst.dtype == VACV_FP32 && interpolation == VACV_INTER_CUBIC)
-            return dtype_convert(src, dst, s);
+        if (src.dtype == VACV_INT8 && dst.dtype == VACV_FP32 && interpolation == VACV_INTER_CUBIC) {
+            if (dense(src) && dense(dst)) return dtype_convert(src, dst, s);
+            // a pitched source or destination (accepted at every other output
+            // size): the same widening, row by row
+            CopyLaunch L{};
+            L.src = geom(src);
+            L.dst = geom(dst);
+            L.n = src.n;
+            L.row_bytes = (int64_t)src.w * (src.layout == VACV_NHWC ? src.c : 1);
+            return hip_status(launch_u8_to_f32_rows(L, s));
+        }
     }
     return resize_impl(src_d, dst_d, interpolation, mode, kOutSame, nullptr, s);
 }

@@ -246,6 +246,8 @@ struct DtypeLaunch {
     int to_f32;                    // 1: u8 -> f32, 0: f32 -> u8
 };
 hipError_t launch_dtype(const DtypeLaunch& L, hipStream_t s);
+// u8 -> f32 between pitched images: CopyLaunch geometry, row_bytes = u8 elements per row
+hipError_t launch_u8_to_f32_rows(const CopyLaunch& L, hipStream_t s);
 
 struct ColorLaunch {
     const unsigned char* src;      // Y plane of image 0

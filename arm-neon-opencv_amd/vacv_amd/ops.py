@@ -123,26 +123,32 @@ def crop(src: torch.Tensor, rect: Sequence[float], layout: int = NHWC, out=None,
     return _shape_back(o4, src, layout)
 
 
-def change_layout(src: torch.Tensor, to_layout: int, layout: int = NHWC, stream=None) -> torch.Tensor:
-    """Tensor::change_layout (tensor.cpp:393-457)."""
+def change_layout(src: torch.Tensor, to_layout: int, layout: int = NHWC, out=None, stream=None) -> torch.Tensor:
+    """Tensor::change_layout (tensor.cpp:393-457).  Across layouts both images
+    must be dense; `out` (optional) is a preallocated 4-D output."""
     s4 = _as4d(src, layout)
     if layout == NHWC:
         n, h, w, c = s4.shape
     else:
         n, c, h, w = s4.shape
-    out = torch.empty((n, h, w, c) if to_layout == NHWC else (n, c, h, w), dtype=src.dtype, device=src.device)
+    if out is None:
+        out = torch.empty((n, h, w, c) if to_layout == NHWC else (n, c, h, w), dtype=src.dtype, device=src.device)
     check("vacv_change_layout", L.load().vacv_change_layout(ctypes.byref(describe(s4, layout)),
                                                             ctypes.byref(describe(out, to_layout)), _stream(stream)))
     return out
 
 
-def change_dtype(src: torch.Tensor, dtype: torch.dtype, layout: int = NHWC, stream=None) -> torch.Tensor:
-    """Tensor::change_dtype (tensor.cpp:459-502): u8<->fp32."""
+def change_dtype(src: torch.Tensor, dtype: torch.dtype, layout: int = NHWC, out=None, stream=None) -> torch.Tensor:
+    """Tensor::change_dtype (tensor.cpp:459-502): u8<->fp32 between dense
+    images; equal dtypes copy (pitches allowed).  `out` (optional) is a
+    preallocated output of the source's shape and dtype `dtype`."""
     s4 = _as4d(src, layout)
-    out = torch.empty(s4.shape, dtype=dtype, device=src.device)
+    if out is None:
+        out = torch.empty(s4.shape, dtype=dtype, device=src.device)
+    o4 = _as4d(out, layout)
     check("vacv_change_dtype", L.load().vacv_change_dtype(ctypes.byref(describe(s4, layout)),
-                                                          ctypes.byref(describe(out, layout)), _stream(stream)))
-    return _shape_back(out, src, layout)
+                                                          ctypes.byref(describe(o4, layout)), _stream(stream)))
+    return _shape_back(o4, src, layout)
 
 
 def resize(src: torch.Tensor, w: int, h: int, interpolation: int = INTER_LINEAR, mode: int = LINEAR_REFERENCE,

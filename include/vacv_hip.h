@@ -106,13 +106,19 @@ int64_t vacv_image_bytes(const vacv_image* img);
 int vacv_crop(const vacv_image* src, const vacv_image* dst, int left, int top, void* stream);
 
 /* Tensor::change_layout (tensor.cpp:393-457): NHWC <-> NCHW of 1,2,4 or 8
- * byte elements.  Same layout or c == 1 is a plain copy (clone()). */
+ * byte elements.  Same layout is a plain copy (clone()) and takes pitched
+ * images.  Across layouts (c == 1 included, a copy too) both images must be
+ * dense -- no row, plane or batch padding -- or the call returns
+ * VACV_ERR_UNSUPPORTED and writes nothing. */
 int vacv_change_layout(const vacv_image* src, const vacv_image* dst, void* stream);
 
 /* Tensor::change_dtype (tensor.cpp:459-502): INT8 -> FP32 exact; FP32 ->
  * INT8 with the NEON f32_2_u8_neon semantics (truncate; NaN/negative -> 0;
- * low 8 bits kept).  Same dtype is a copy; other pairs VACV_ERR_UNSUPPORTED
- * (the reference silently returns an uninitialised tensor). */
+ * low 8 bits kept: +inf and values >= 2^32 -> 255, 256.7 -> 0).  Same dtype
+ * is a copy and takes pitched images; INT8 <-> FP32 needs both images dense
+ * (VACV_ERR_UNSUPPORTED otherwise, nothing written); other pairs
+ * VACV_ERR_UNSUPPORTED (the reference silently returns an uninitialised
+ * tensor). */
 int vacv_change_dtype(const vacv_image* src, const vacv_image* dst, void* stream);
 
 /* Resize::resize (resize.cpp:19-100, cv.h:85-87).  Only dst->w/h select the
@@ -129,7 +135,10 @@ int vacv_change_dtype(const vacv_image* src, const vacv_image* dst, void* stream
  *                blocks of 1/3/4 channels half up), other down-scales =
  *                resizeArea_'s weight tables, up-scales = its bilinear with
  *                area-mode taps (parity unpinned).
- * NHWC channels 1..4; NCHW any c (per plane, as resize.cpp:72-88). */
+ * NHWC channels 1..4; NCHW any c (per plane, as resize.cpp:72-88).
+ * INTER_LINEAR / INTER_CUBIC with dst->w/h == src->w/h copy the source
+ * (resize.cpp:58-61; INT8 -> FP32 under INTER_CUBIC widens it), pitched
+ * images included, as at every other size. */
 int vacv_resize(const vacv_image* src, const vacv_image* dst, int interpolation, int mode, void* stream);
 
 /* vacv_resize with cv::resize's explicit scale factors (the reference passes
@@ -198,7 +207,8 @@ int vacv_cvt_color(const vacv_image* src, const vacv_image* dst, int code, void*
  *   dst = (float)(((float)x - mean[k]) / ((double)stddev[k] + 1e-6))
  * src INT8 or FP32, dst FP32, same layout.  mean/stddev are HOST arrays of
  * c floats; both NULL = per-image statistics first (exact, see
- * vacv_mean_stddev).  Exactly one NULL is VACV_ERR_INVALID_ARG. */
+ * vacv_mean_stddev; src must then be dense).  Exactly one NULL is
+ * VACV_ERR_INVALID_ARG.  With host mean/stddev src and dst may be pitched. */
 int vacv_normalize(const vacv_image* src, const vacv_image* dst,
                    const float* mean, const float* stddev, void* stream);
 
@@ -206,7 +216,9 @@ int vacv_normalize(const vacv_image* src, const vacv_image* dst,
  * sums[g*2c + 2k + 1] = Sum x^2 over channel k, g = image (per_image=1) or
  * the whole batch (per_image=0, one group).  DEVICE output, fp64; exact for
  * INT8 input (integer sums), deterministic order for FP32.  These are the
- * partials the multi-GPU path all-reduces over RCCL. */
+ * partials the multi-GPU path all-reduces over RCCL.  src must be dense (no
+ * row, plane or batch padding; VACV_ERR_UNSUPPORTED otherwise) with NHWC
+ * c <= 4; any base address works, 16-byte aligned images are faster. */
 int vacv_channel_sums(const vacv_image* src, double* sums, int per_image, void* stream);
 
 /* vacv_resize followed by vacv_channel_sums of its output: the statistics
@@ -233,7 +245,8 @@ int vacv_stats_from_sums(const double* sums, int groups, int c, double count,
 
 /* NormalizeNaive::mean_stddev_naive_* (normalize_naive.cpp:7-72): per-image
  * population mean/stddev, DEVICE outputs [n][c].  Computed exactly (the
- * reference accumulates sequentially in fp32; DESIGN.md quantifies it). */
+ * reference accumulates sequentially in fp32; DESIGN.md quantifies it).
+ * src must be dense, as for vacv_channel_sums (VACV_ERR_UNSUPPORTED). */
 int vacv_mean_stddev(const vacv_image* src, float* mean, float* stddev, void* stream);
 
 /* ---- fused pipelines -------------------------------------------------- */

@@ -49,7 +49,11 @@ def test_version_and_status(lib):
     assert len(vacv_amd._lib.TUNE) == count and sorted(vacv_amd._lib.TUNE.values()) == list(range(count))
     for name, key in vacv_amd._lib.TUNE.items():
         assert re.search(rf"VACV_TUNE_{name} = {key},", hdr), name
-    assert lib.vacv_set_tuning(count - 1, -1) == 0 and lib.vacv_set_tuning(count, -1) == -1
+    # the last key is settable and the one after it is not; write back the
+    # current value (as _lib.load() does) so an environment override survives
+    last = lib.vacv_get_tuning(count - 1)
+    assert lib.vacv_set_tuning(count - 1, last) == 0 and lib.vacv_set_tuning(count, -1) == -1
+    assert lib.vacv_get_tuning(count - 1) == last
     assert lib.vacv_status_string(0) == b"ok"
     assert lib.vacv_status_string(-2) == b"unsupported"
 

@@ -703,19 +703,22 @@ def test_resize_strip_kernel(ops, dev, oracle):
                     assert torch.equal(a, b), f"strip{sv} vs staged {wo}x{ho} mode {mode}"
     s1 = to_dev(big[0][None, :200, :320].copy(), dev)
     for wo, ho, dt in [(211, 150, torch.uint8), (200, 151, torch.uint8), (150, 140, torch.float32)]:
-        buf = torch.zeros((1, ho + 9, wo + 23, 3), dtype=dt, device=dev)
-        view = buf[:, 4:4 + ho, 7:7 + wo]
-        with ops.tuning(RESIZE_STRIP=1):
-            if dt == torch.uint8:
-                ops.resize(s1, wo, ho, out=view)
-                want = oracle.resize_linear(big[0][:200, :320].copy(), wo, ho)
-            else:
-                ops.resize_normalize(s1, wo, ho, MEAN, STD, out=view)
-                want = oracle.normalize(oracle.u8_to_f32(oracle.resize_linear(big[0][:200, :320].copy(), wo, ho)), MEAN, STD)
-        got = host(buf)
-        assert_same(got[0, 4:4 + ho, 7:7 + wo], want, f"strip pitched out {wo}x{ho} {dt}")
-        got[0, 4:4 + ho, 7:7 + wo] = 0
-        assert not got.any(), f"strip pitched out {wo}x{ho}: wrote outside the window"
+        if dt == torch.uint8:
+            want = oracle.resize_linear(big[0][:200, :320].copy(), wo, ho)
+        else:
+            want = oracle.normalize(oracle.u8_to_f32(oracle.resize_linear(big[0][:200, :320].copy(), wo, ho)), MEAN, STD)
+        for sv in (1, 2):  # 64- and 128-column strips
+            buf = torch.zeros((1, ho + 9, wo + 23, 3), dtype=dt, device=dev)
+            view = buf[:, 4:4 + ho, 7:7 + wo]
+            with ops.tuning(RESIZE_STRIP=sv):
+                if dt == torch.uint8:
+                    ops.resize(s1, wo, ho, out=view)
+                else:
+                    ops.resize_normalize(s1, wo, ho, MEAN, STD, out=view)
+            got = host(buf)
+            assert_same(got[0, 4:4 + ho, 7:7 + wo], want, f"strip{sv} pitched out {wo}x{ho} {dt}")
+            got[0, 4:4 + ho, 7:7 + wo] = 0
+            assert not got.any(), f"strip{sv} pitched out {wo}x{ho}: wrote outside the window"
 
 
 def test_resize_normalize(ops, dev, oracle):
@@ -1025,6 +1028,24 @@ def test_match_template(ops, dev, oracle):
     for m in (1, 5):
         assert_same(host(ops.match_template(to_dev(wide[None], dev), to_dev(wtpl, dev), m))[0],
                     oracle.match_template(wide, wtpl, m), f"match integral images wide row method {m}")
+    # the boundary between the two: match_finish_u8_kernel's LDS is 2 (iw + 1) cn
+    # dwords of prefix rows plus its static wave totals (2 x 4 x 4 dwords = 128
+    # bytes), within 64 KiB: (iw + 1) cn <= (65,536 - 128) / 8 = 8,176, so the
+    # widest box-sum image is 8,175 pixels for cn = 1 and 2,043 for cn = 4, and
+    # one pixel more (8,176 / 2,044) takes the integral images.  Both against
+    # the oracle, and equal on the columns they share of one common image.
+    for c in (1, 4):
+        wbox = (64 * 1024 - 2 * 4 * 4 * 4) // (8 * c) - 1
+        assert wbox == {1: 8175, 4: 2043}[c]
+        edge = synthetic_image(990 + c, 9, wbox + 1, c).reshape(9, wbox + 1, c)
+        etpl = np.ascontiguousarray(edge[1:8, 50:59])  # 7 rows x 9 columns
+        for m in (1, 5):
+            box = host(ops.match_template(to_dev(np.ascontiguousarray(edge[None, :, :wbox]), dev), to_dev(etpl, dev), m))[0]
+            integ = host(ops.match_template(to_dev(edge[None], dev), to_dev(etpl, dev), m))[0]
+            assert_same(box, oracle.match_template(np.ascontiguousarray(edge[:, :wbox]), etpl, m),
+                        f"match widest box sums c{c} method {m}")
+            assert_same(integ, oracle.match_template(edge, etpl, m), f"match narrowest integral images c{c} method {m}")
+            assert_same(integ[:, :box.shape[1]], box, f"match box sums vs integral images c{c} method {m}")
     # minMaxIdx on a match result finds the template's position
     got = ops.match_template(to_dev(img, dev), to_dev(small, dev), 0)
     mn, mx, imn, imx = ops.min_max_idx(got)
