@@ -1,0 +1,368 @@
+// k_warp_rois.hip -- many small affine crops in one launch: ROI i of the
+// destination is warp_affine of source frame src_index[i] under its own 2x3
+// map m[i], both read from DEVICE arrays when the kernel runs.
+//
+// The per-pixel arithmetic is warp_kernel's (k_warp.hip), bit for bit:
+// f = inv0*x + (inv1*y) + inv2 in float, affine_tap, u8 weights
+// (int)((1-a)*2048+0.5f), v_perm + v_dot2 + 24-bit multiplies >> 22; fp32
+// left to right.  What differs is the shape of the work:
+//  * a workgroup owns kTile CONSECUTIVE pixels of one ROI's row-major pixel
+//    index (a band of ROI rows), and a wave's gather samples 64 consecutive
+//    ones, so a 112-, 140- or 37-wide ROI fills every lane (warp_kernel's
+//    512 x 4 tile leaves most of them outside such an image);
+//  * the map is inverted on the device (invert_affine_value, the host's own
+//    function) once per workgroup;
+//  * every source read of the sampler goes through a buffer resource that
+//    spans exactly the indexed frame; an index outside [0, n_src) gives a
+//    resource of zero bytes and a ROI of border_value without a single read.
+// A dense ROI (row pitch = row bytes) is one contiguous byte range per plane,
+// so the band leaves LDS as 16-byte stores whatever the ROI width: the band
+// is laid out in LDS at the destination's own offset modulo 16 (head and tail
+// bytes singly).  Pitched ROIs go row by row through the same copy.
+#pragma clang fp contract(off)
+
+#include "vacv_device.hpp"
+
+namespace vacv {
+namespace {
+
+constexpr int kRoiPx = 4;                // 64-pixel gathers per wave
+constexpr int kRoiTile = kBlock * kRoiPx;  // pixels per workgroup
+
+// p / w and p % w for p < w + kRoiTile, w <= 2^20 (rw = 1.f / w): the float
+// quotient is within one of the true one, the remainder test settles it
+__device__ __forceinline__ void divmod_w(uint32_t p, uint32_t w, float rw, int& q, int& r) {
+    int qq = (int)((float)p * rw);
+    int rr = (int)p - qq * (int)w;
+    if (rr < 0) { --qq; rr += (int)w; }
+    else if (rr >= (int)w) { ++qq; rr -= (int)w; }
+    q = qq;
+    r = rr;
+}
+
+__device__ __forceinline__ float uniform_f(float v) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
+}
+
+// nbytes from LDS offset `lo` of xch (16-byte aligned) to d, by threads t of
+// nt: 16-byte stores where LDS offset and destination agree modulo 16,
+// dwords where they agree modulo 4, else bytes; heads and tails bytewise.
+// The loops stay rolled: a band is at most a few 16-byte chunks per thread,
+// and the unrolled copies held the kernel at half of warp_kernel's occupancy.
+__device__ __forceinline__ void copy_run(unsigned char* d, const unsigned char* xch, uint32_t lo, int nbytes, int t,
+                                         int nt) {
+    const uintptr_t da = reinterpret_cast<uintptr_t>(d);
+    const unsigned char* xs = xch + lo;
+    const uint32_t diff = ((uint32_t)da ^ lo);
+    if ((diff & 15u) == 0) {  // uniform per run
+        const int head = min(nbytes, (int)((16u - ((uint32_t)da & 15u)) & 15u));
+        const int nmid = (nbytes - head) >> 4;
+#pragma unroll 1
+        for (int e = t; e < head; e += nt) d[e] = xs[e];
+#pragma unroll 1
+        for (int c = t; c < nmid; c += nt)
+            __builtin_nontemporal_store(*reinterpret_cast<const u32x4*>(xs + head + 16 * c),
+                                        reinterpret_cast<u32x4*>(d + head) + c);
+#pragma unroll 1
+        for (int e = head + 16 * nmid + t; e < nbytes; e += nt) d[e] = xs[e];
+    } else if ((diff & 3u) == 0) {
+        const int head = min(nbytes, (int)((4u - ((uint32_t)da & 3u)) & 3u));
+        const int nmid = (nbytes - head) >> 2;
+#pragma unroll 1
+        for (int e = t; e < head; e += nt) d[e] = xs[e];
+#pragma unroll 1
+        for (int c = t; c < nmid; c += nt)
+            reinterpret_cast<uint32_t*>(d + head)[c] = *reinterpret_cast<const uint32_t*>(xs + head + 4 * c);
+#pragma unroll 1
+        for (int e = head + 4 * nmid + t; e < nbytes; e += nt) d[e] = xs[e];
+    } else {
+#pragma unroll 1
+        for (int e = t; e < nbytes; e += nt) d[e] = xs[e];
+    }
+}
+
+// N consecutive floats at buffer byte offset `off`, one range-checked dword
+// load each (the compiler merges neighbours where it can prove it may)
+template <int N>
+__device__ __forceinline__ void load_f32(const Rsrc& rs, uint32_t off, float (&v)[N]) {
+#pragma unroll
+    for (int i = 0; i < N; ++i)
+        v[i] = __builtin_bit_cast(float, (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs.r, (int)(off + 4u * i), 0, 0));
+}
+
+// PLANAR: fp32 NCHW destination (one LDS region and one byte range per plane)
+// EXT: border modes other than CONSTANT (a separate instance, as warp_kernel)
+template <int CC, typename TIn, int OUT, bool PLANAR, bool EXT>
+__global__ void __launch_bounds__(kBlock)
+warp_rois_kernel(WarpRoisLaunch L, int tiles, int total) {
+    using TOut = typename std::conditional<(OUT == kOutSame), TIn, float>::type;
+    constexpr bool kU8 = std::is_same<TIn, uint8_t>::value;
+    constexpr bool kU8Norm = kU8 && (OUT == kOutNorm);
+    constexpr int kPlanes = PLANAR ? CC : 1;
+    constexpr int kPxB = (PLANAR ? 1 : CC) * (int)sizeof(TOut);  // bytes per pixel of one destination plane
+    constexpr int kRegion = kRoiTile * kPxB + 16;                // + the destination's offset modulo 16
+    __shared__ __attribute__((aligned(16))) unsigned char xch[kPlanes * kRegion];
+    __shared__ float s_inv[6];
+    __shared__ int s_frame;
+
+    // XCD-aware block order (see warp_kernel): an XCD walks a contiguous
+    // range of (ROI, tile), so the tiles of one ROI, which share source lines,
+    // meet in one L2
+    const int per_xcd = (total + 7) / 8;
+    const int id = (int)(blockIdx.x % 8) * per_xcd + (int)(blockIdx.x / 8);
+    if (id >= total) return;  // uniform
+    const int roi = id / tiles;
+    const int tile = id - roi * tiles;
+    // the wave index as a scalar: the per-run addresses of the pitched epilogue stay in SGPRs
+    const int lane = threadIdx.x, wv = __builtin_amdgcn_readfirstlane((int)threadIdx.y);
+    const int tid = wv * 64 + lane;
+
+    // ---- the ROI's map and frame: one thread reads the device arrays and inverts
+    if (tid == 0) {
+        float m[6], inv[6];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) m[k] = L.m[(int64_t)roi * 6 + k];
+        if (L.inverse_map) {
+#pragma unroll
+            for (int k = 0; k < 6; ++k) inv[k] = m[k];
+        } else {
+            invert_affine_value(m, inv);
+        }
+#pragma unroll
+        for (int k = 0; k < 6; ++k) s_inv[k] = inv[k];
+        s_frame = L.src_index ? L.src_index[roi] : (L.n_src == 1 ? 0 : roi);
+    }
+    __syncthreads();
+    // into scalar registers: everything derived from them (the frame's buffer
+    // resource above all) is then uniform for the compiler too
+    const float i0 = uniform_f(s_inv[0]), i1 = uniform_f(s_inv[1]), i2 = uniform_f(s_inv[2]);
+    const float i3 = uniform_f(s_inv[3]), i4 = uniform_f(s_inv[4]), i5 = uniform_f(s_inv[5]);
+    const int frame = __builtin_amdgcn_readfirstlane(s_frame);
+    const bool valid = frame >= 0 && frame < L.n_src;  // uniform; else: all border, nothing read
+
+    float nmean[CC], nstd[CC];
+    if (OUT == kOutNorm) {
+#pragma unroll
+        for (int k = 0; k < CC; ++k) norm_params(L.norm, 0, k, nmean[k], nstd[k]);
+    }
+    ChanNorm cn[CC] = {};
+    if (kU8Norm) {
+#pragma unroll
+        for (int k = 0; k < CC; ++k) cn[k] = chan_norm(L.norm, 0, k);
+    }
+    TOut bval[CC];
+#pragma unroll
+    for (int k = 0; k < CC; ++k) {
+        if (OUT == kOutNorm)
+            bval[k] = kU8Norm ? (TOut)normalize_u8v(cn[k], (int)L.border[k])
+                              : (TOut)normalize_value(L.border[k], nmean[k], nstd[k]);
+        else
+            bval[k] = (TOut)L.border[k];
+    }
+
+    const unsigned char* sp = L.src.base + (int64_t)(valid ? frame : 0) * L.src.img_pitch;
+    const int64_t rp = L.src.row_pitch;
+    const Rsrc srs = make_rsrc(sp, valid ? L.src.plane_bytes : 0);
+    const uint32_t slimit = (valid ? (uint32_t)L.src.plane_bytes : 0u) + srs.delta;
+    const uint32_t rp32 = (uint32_t)rp;  // plane_bytes <= kMaxPlaneBytes (launch_warp_rois)
+    const bool mul24 = rp < (1 << 24) && L.src.h < (1 << 24);
+
+    // ---- the tile: pixels [p0, p0 + npx) of the ROI, first one at (tx0, ty0)
+    const int w = L.dst.w;
+    const int roi_px = w * L.dst.h;
+    const int p0 = tile * kRoiTile;
+    const int npx = min(kRoiTile, roi_px - p0);
+    const int ty0 = p0 / w, tx0 = p0 - ty0 * w;  // uniform
+    const float rw = 1.f / (float)w;
+    unsigned char* dbase = const_cast<unsigned char*>(L.dst.base) + (int64_t)roi * L.dst.img_pitch;
+    const bool dense = L.dst.row_pitch == (int64_t)w * kPxB;  // the band is one byte range per plane
+    uint32_t shift[kPlanes];
+#pragma unroll
+    for (int k = 0; k < kPlanes; ++k) {
+        const uintptr_t a = reinterpret_cast<uintptr_t>(dbase + (int64_t)k * L.dst.plane_pitch + (int64_t)p0 * kPxB);
+        shift[k] = dense ? ((uint32_t)a & 15u & ~(uint32_t)(sizeof(TOut) - 1)) : 0u;
+    }
+
+#pragma unroll
+    for (int q = 0; q < kRoiPx; ++q) {
+        const int loc = (wv * kRoiPx + q) * 64 + lane;  // 64 consecutive pixels per gather
+        if (loc >= npx) continue;
+        int dy, x;
+        divmod_w((uint32_t)(tx0 + loc), (uint32_t)w, rw, dy, x);
+        const int y = ty0 + dy;
+        TOut* o[CC];
+#pragma unroll
+        for (int k = 0; k < CC; ++k)
+            o[k] = PLANAR ? reinterpret_cast<TOut*>(xch + k * kRegion + shift[k]) + loc
+                          : reinterpret_cast<TOut*>(xch + shift[0]) + loc * CC + k;
+        // warp_affine_naive.cpp:23-24: (m0*x + m1*y) + m2, all float
+        const float fx = i0 * (float)x + i1 * (float)y + i2;
+        const float fy = i3 * (float)x + i4 * (float)y + i5;
+        int sx = 0, sy = 0;
+        float ax = 0.f, ay = 0.f;
+        const bool ok = valid && affine_tap(fy, L.src.h, sy, ay) && affine_tap(fx, L.src.w, sx, ax);
+        if (!ok) {
+            if (EXT && valid) {  // L.border_mode != kBorderConstant
+                int vi[CC];
+                float vf[CC];
+                warp_border_sample<CC, TIn>(sp, rp, L.src.w, L.src.h, L.border_mode, fx, fy, vi, vf);
+#pragma unroll
+                for (int k = 0; k < CC; ++k) {
+                    if (kU8) {
+                        if (OUT == kOutSame) *o[k] = (TOut)vi[k];
+                        else *o[k] = (TOut)normalize_u8v(cn[k], vi[k]);
+                    } else {
+                        *o[k] = (TOut)(OUT == kOutNorm ? normalize_value(vf[k], nmean[k], nstd[k]) : vf[k]);
+                    }
+                }
+                continue;
+            }
+#pragma unroll
+            for (int k = 0; k < CC; ++k) *o[k] = bval[k];
+            continue;
+        }
+        const uint32_t o0 = (mul24 ? __umul24((uint32_t)sy, rp32) : (uint32_t)sy * rp32) +
+                            (uint32_t)(sx * CC * (int)sizeof(TIn)) + srs.delta;
+        const uint32_t o1 = o0 + rp32;
+        if constexpr (kU8) {
+            // SATURATE_CAST_SHORT of a value in (0, 2048]: the +0.5f branch, no clamp
+            const int wy0 = (int)((1.f - ay) * 2048.f + 0.5f), wy1 = 2048 - wy0;
+            const int wx0 = (int)((1.f - ax) * 2048.f + 0.5f), wx1 = 2048 - wx0;
+            // the 2*CC tap bytes of each row in ONE dword-aligned buffer load;
+            // a load past the frame's end (its last pixel) falls back to bytes
+            uint32_t a0 = 0, a1 = 0, c0 = 0, c1 = 0;
+            if ((o1 & ~3u) + 4u * kTapDwords<CC, true> <= slimit) {
+                load_taps<CC, true, 0>(srs, o0, a0, a1);
+                load_taps<CC, true, 0>(srs, o1, c0, c1);
+            } else {
+#pragma unroll
+                for (int e = 0; e < 2 * CC; ++e) {
+                    const uint32_t t0 = __builtin_amdgcn_raw_buffer_load_b8(srs.r, (int)(o0 + e), 0, 0);
+                    const uint32_t t1 = __builtin_amdgcn_raw_buffer_load_b8(srs.r, (int)(o1 + e), 0, 0);
+                    if (e < 4) { a0 |= t0 << (8 * e); c0 |= t1 << (8 * e); }
+                    else { a1 |= t0 << (8 * (e - 4)); c1 |= t1 << (8 * (e - 4)); }
+                }
+            }
+            // warp_affine_naive.cpp:50-54 as (tl*wx0 + tr*wx1)*wy0 + (bl*wx0 +
+            // br*wx1)*wy1: the same int32 value (exact, <= 255*2^22)
+            const us2 wx = __builtin_bit_cast(us2, (uint32_t)wx0 | ((uint32_t)wx1 << 16));
+#pragma unroll
+            for (int k = 0; k < CC; ++k) {
+                const uint32_t sel = (uint32_t)k | (0x0Cu << 8) | ((uint32_t)(CC + k) << 16) | (0x0Cu << 24);
+                const uint32_t top = __builtin_amdgcn_perm(a1, a0, sel);
+                const uint32_t bot = __builtin_amdgcn_perm(c1, c0, sel);
+                const uint32_t ht = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, top), wx, 0u, false);
+                const uint32_t hb = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, bot), wx, 0u, false);
+                const int v = (int)((__umul24(ht, (uint32_t)wy0) + __umul24(hb, (uint32_t)wy1)) >> 22);
+                if (OUT == kOutSame) *o[k] = (TOut)v;
+                else *o[k] = (TOut)normalize_u8v(cn[k], v);
+            }
+        } else {
+            const float yy0 = 1.f - ay, yy1 = ay, xa = 1.f - ax, xb = ax;
+            float f0[2 * CC], f1[2 * CC];
+            load_f32<2 * CC>(srs, o0, f0);
+            load_f32<2 * CC>(srs, o1, f1);
+#pragma unroll
+            for (int k = 0; k < CC; ++k) {
+                // warp_affine_naive.cpp:98-102, left to right
+                float v = f0[k] * xa * yy0;
+                v += f1[k] * xa * yy1;
+                v += f0[CC + k] * xb * yy0;
+                v += f1[CC + k] * xb * yy1;
+                if (OUT == kOutNorm) v = normalize_value(v, nmean[k], nstd[k]);
+                *o[k] = (TOut)v;
+            }
+        }
+    }
+    __syncthreads();
+
+    // ---- LDS -> HBM -----------------------------------------------------------
+    if (dense) {  // uniform: one byte range per plane, all four waves on it
+#pragma unroll
+        for (int k = 0; k < kPlanes; ++k)
+            copy_run(dbase + (int64_t)k * L.dst.plane_pitch + (int64_t)p0 * kPxB, xch, (uint32_t)(k * kRegion) + shift[k],
+                     npx * kPxB, tid, kBlock);
+        return;
+    }
+    // pitched rows: wave r % 4 copies run r = (plane, band row)
+    int dy1, x1;
+    divmod_w((uint32_t)(tx0 + npx - 1), (uint32_t)w, rw, dy1, x1);
+    const int nrows = dy1 + 1;
+#pragma unroll 1
+    for (int r = wv; r < kPlanes * nrows; r += 4) {
+        const int k = PLANAR ? r / nrows : 0;
+        const int dy = r - k * nrows;
+        const int xa = dy == 0 ? tx0 : 0;
+        const int xb = dy == dy1 ? x1 + 1 : w;
+        const int loc = dy * w + xa - tx0;  // tile-local index of the run's first pixel
+        copy_run(dbase + (int64_t)k * L.dst.plane_pitch + (int64_t)(ty0 + dy) * L.dst.row_pitch + (int64_t)xa * kPxB, xch,
+                 (uint32_t)(k * kRegion + loc * kPxB), (xb - xa) * kPxB, lane, 64);
+    }
+}
+
+// inv[i] = invert_affine_value(m[i]): one map per thread
+__global__ void __launch_bounds__(kBlock) invert_affine_kernel(const float* m, float* inv, int n) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    float a[6], b[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) a[k] = m[(int64_t)i * 6 + k];
+    invert_affine_value(a, b);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) inv[(int64_t)i * 6 + k] = b[k];
+}
+
+template <int CC, typename TIn, int OUT, bool PLANAR>
+hipError_t launch_ext(const WarpRoisLaunch& L, hipStream_t s) {
+    const int64_t px = (int64_t)L.dst.w * L.dst.h;
+    const int64_t tiles = (px + kRoiTile - 1) / kRoiTile;
+    const int64_t total = tiles * L.n_roi;
+    if (total >= 0x7FFFFFF0LL) return hipErrorInvalidValue;
+    const int64_t blocks = (total + 7) / 8 * 8;
+    if (L.border_mode == kBorderConstant)
+        hipLaunchKernelGGL((warp_rois_kernel<CC, TIn, OUT, PLANAR, false>), dim3((unsigned)blocks), dim3(64, 4), 0, s, L,
+                           (int)tiles, (int)total);
+    else
+        hipLaunchKernelGGL((warp_rois_kernel<CC, TIn, OUT, PLANAR, true>), dim3((unsigned)blocks), dim3(64, 4), 0, s, L,
+                           (int)tiles, (int)total);
+    return hipGetLastError();
+}
+
+template <typename TIn, int OUT>
+hipError_t launch_cc(const WarpRoisLaunch& L, hipStream_t s) {
+    if (L.planar) {
+        if constexpr (OUT == kOutNorm) {
+            if (L.src.cc == 3) return launch_ext<3, TIn, OUT, true>(L, s);
+        }
+        return hipErrorInvalidValue;
+    }
+    switch (L.src.cc) {
+        case 1: return launch_ext<1, TIn, OUT, false>(L, s);
+        case 2: return launch_ext<2, TIn, OUT, false>(L, s);
+        case 3: return launch_ext<3, TIn, OUT, false>(L, s);
+        case 4: return launch_ext<4, TIn, OUT, false>(L, s);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+}  // namespace
+
+hipError_t launch_warp_rois(const WarpRoisLaunch& L, hipStream_t s) {
+    // the kernel's 32-bit source offsets, its float row/column split
+    // (divmod_w) and its int pixel index
+    if (L.src.plane_bytes > kMaxPlaneBytes || L.dst.w > (1 << 20) || (int64_t)L.dst.w * L.dst.h > 0x7FFF0000LL)
+        return hipErrorInvalidValue;
+    if (L.src.esize == 1) {
+        if (L.out == kOutSame) return launch_cc<uint8_t, kOutSame>(L, s);
+        return launch_cc<uint8_t, kOutNorm>(L, s);
+    }
+    if (L.out == kOutNorm) return launch_cc<float, kOutNorm>(L, s);
+    return launch_cc<float, kOutSame>(L, s);
+}
+
+hipError_t launch_invert_affine(const float* m, float* inv, int n, hipStream_t s) {
+    hipLaunchKernelGGL(invert_affine_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, m, inv, n);
+    return hipGetLastError();
+}
+
+}  // namespace vacv

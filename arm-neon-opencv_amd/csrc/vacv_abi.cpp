@@ -476,6 +476,48 @@ int warp_impl(const vacv_image* src_d, const vacv_image* dst_d, const float m[6]
     return hip_status(launch_warp(L, s));
 }
 
+// vacv_warp_affine_rois[_normalize]: dst image i = warp of src image
+// src_index[i] under m[i].  m and src_index are device arrays: validated for
+// presence only, never read here.  ns: host-constant statistics (fp32 output,
+// NHWC or planar), or null (dst like src).
+int warp_rois_impl(const vacv_image* src_d, const vacv_image* dst_d, const float* m, const int32_t* src_index,
+                   int flags, int border_mode, const double bv[4], const NormSpec* ns, hipStream_t s) {
+    Img src, dst;
+    int st = load(src_d, src);
+    if (st) return st;
+    if ((st = load(dst_d, dst))) return st;
+    if (!m) return VACV_ERR_INVALID_ARG;
+    if (src.c != dst.c) return VACV_ERR_INVALID_ARG;
+    if (!src_index && src.n != 1 && src.n != dst.n) return VACV_ERR_INVALID_ARG;
+    if (src.dtype != VACV_INT8 && src.dtype != VACV_FP32) return VACV_ERR_UNSUPPORTED;
+    if (src.layout != VACV_NHWC) return VACV_ERR_UNSUPPORTED;
+    if (flags & ~(7 | VACV_WARP_INVERSE_MAP)) return VACV_ERR_UNSUPPORTED;
+    if ((flags & 7) != VACV_INTER_LINEAR) return VACV_ERR_UNSUPPORTED;
+    if (border_mode < VACV_BORDER_CONSTANT || border_mode >= VACV_BORDER_TRANSPARENT) return VACV_ERR_UNSUPPORTED;
+    if (src.c > 4) return VACV_ERR_UNSUPPORTED;
+    if (src.w < 2 || src.h < 2) return VACV_ERR_INVALID_ARG;
+    if (dst.dtype != (ns ? VACV_FP32 : src.dtype)) return VACV_ERR_INVALID_ARG;
+    if (!ns && dst.layout != VACV_NHWC) return VACV_ERR_INVALID_ARG;  // dst layout = src's
+    // planar output: 3 channels; one channel is the same bytes either way
+    const bool planar = dst.layout == VACV_NCHW && dst.c > 1;
+    if (planar && dst.c != 3) return VACV_ERR_UNSUPPORTED;
+    WarpRoisLaunch L{};
+    L.src = geom(src);
+    if (L.src.plane_bytes > kMaxPlaneBytes) return VACV_ERR_UNSUPPORTED;
+    L.dst = geom(dst);
+    L.n_src = src.n;
+    L.n_roi = dst.n;
+    L.m = m;
+    L.src_index = src_index;
+    L.inverse_map = (flags & VACV_WARP_INVERSE_MAP) != 0;
+    border_values(src, bv, L.border);
+    L.border_mode = border_mode;
+    L.out = ns ? kOutNorm : kOutSame;
+    L.planar = planar;
+    if (ns) L.norm = *ns;
+    return hip_status(launch_warp_rois(L, s));
+}
+
 int color_code(int code, int& v_first, int& rgb) {
     switch (code) {
         case VACV_COLOR_YUV2BGR_NV21: v_first = 1; rgb = 0; return VACV_OK;
@@ -826,23 +868,35 @@ int vacv_rotation_matrix(float scale, float rot_deg, const double aux[4], float 
 
 int vacv_invert_affine(const float m[6], float inv[6]) {
     if (!m || !inv) return VACV_ERR_INVALID_ARG;
-    // warp_affine.cpp:121-133: float products, double D, stored as float
-    float a[6];
-    std::memcpy(a, m, sizeof(a));
-    double D = (double)(a[0] * a[4] - a[1] * a[3]);
-    D = D != 0 ? 1. / D : 0;
-    const double A11 = (double)a[4] * D;
-    const double A22 = (double)a[0] * D;
-    a[0] = (float)A11;
-    a[1] = (float)((double)a[1] * -D);
-    a[3] = (float)((double)a[3] * -D);
-    a[4] = (float)A22;
-    const float b1 = -a[0] * a[2] - a[1] * a[5];
-    const float b2 = -a[3] * a[2] - a[4] * a[5];
-    a[2] = b1;
-    a[5] = b2;
-    std::memcpy(inv, a, sizeof(a));
+    invert_affine_value(m, inv);  // vacv_semantics.hpp: the kernels' own function
     return VACV_OK;
+}
+
+int vacv_invert_affine_device(const float* m, float* inv, int n, void* stream) {
+    if (!m || !inv || n < 0) return VACV_ERR_INVALID_ARG;
+    if (n == 0) return VACV_OK;
+    return hip_status(launch_invert_affine(m, inv, n, (hipStream_t)stream));
+}
+
+int vacv_warp_affine_rois(const vacv_image* src, const vacv_image* dst, const float* m, const int32_t* src_index,
+                          int flags, int border_mode, const double border_value[4], void* stream) {
+    return warp_rois_impl(src, dst, m, src_index, flags, border_mode, border_value, nullptr, (hipStream_t)stream);
+}
+
+int vacv_warp_affine_rois_normalize(const vacv_image* src, const vacv_image* dst, const float* m,
+                                    const int32_t* src_index, int flags, int border_mode,
+                                    const double border_value[4], const float* mean, const float* stddev,
+                                    void* stream) {
+    if (!mean && !stddev) return VACV_ERR_UNSUPPORTED;  // per-image statistics of a ROI: not built
+    if (!mean || !stddev) return VACV_ERR_INVALID_ARG;
+    Img sm, d;
+    int st = load(src, sm);
+    if (st) return st;
+    if ((st = load(dst, d))) return st;
+    if (sm.c != d.c) return VACV_ERR_INVALID_ARG;  // mean / stddev hold the source's c values
+    NormSpec ns;
+    if ((st = norm_spec(d, mean, stddev, ns))) return st;
+    return warp_rois_impl(src, dst, m, src_index, flags, border_mode, border_value, &ns, (hipStream_t)stream);
 }
 
 int vacv_warp_affine(const vacv_image* src, const vacv_image* dst, const float m[6], int flags, int border_mode,

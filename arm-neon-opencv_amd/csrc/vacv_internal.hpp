@@ -199,6 +199,23 @@ hipError_t launch_warp(const WarpLaunch& L, hipStream_t s);
 // INTER_NEAREST (OpenCV 2.4 warpAffine + remapNearest; the reference hands
 // every flag but INTER_LINEAR to OpenCV, warp_affine.cpp:114-118)
 hipError_t launch_warp_nearest(const WarpLaunch& L, hipStream_t s);
+// Many crops in one launch (k_warp_rois.hip): ROI i = warp of frame
+// src_index[i] under m[i]; both arrays are device memory read by the kernel
+struct WarpRoisLaunch {
+    PlaneGeom src;               // NHWC frames (planes = 1)
+    PlaneGeom dst;               // ROI 0; img_pitch between ROIs; planar: plane_pitch between channel planes
+    int n_src, n_roi;
+    const float* m;              // device [n_roi][6]
+    const int32_t* src_index;    // device [n_roi], or null: frame 0 (n_src == 1) or frame i
+    int inverse_map;             // m[i] is already the dst -> src map
+    float border[4];
+    int border_mode;             // kBorder* but TRANSPARENT
+    int out;                     // kOutSame or kOutNorm
+    int planar;                  // fp32 NCHW destination
+    NormSpec norm;
+};
+hipError_t launch_warp_rois(const WarpRoisLaunch& L, hipStream_t s);
+hipError_t launch_invert_affine(const float* m, float* inv, int n, hipStream_t s);
 // u8 CONSTANT warp (1-4 interleaved channels, or NCHW planes) with the source boxes
 // copied into an LDS ring by LDS-DMA and the geometry shared by kf frames per
 // workgroup (k_warp_frames.hip)

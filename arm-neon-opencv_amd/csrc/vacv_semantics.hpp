@@ -124,6 +124,29 @@ VACV_HD bool affine_tap(float f, int n, int& i, float& frac) {
     return true;
 }
 
+// The in-place inverse of warp_affine.cpp:121-133, out of place: float
+// products, the determinant widened to double, an IEEE double reciprocal
+// (0 for a zero determinant: the inverse is then all zeros), results stored
+// as float; every operation separately rounded (the pragma above).  One
+// body for the host entry point and the kernels that invert on the device.
+VACV_HD void invert_affine_value(const float m[6], float inv[6]) {
+    float a[6];
+    for (int k = 0; k < 6; ++k) a[k] = m[k];
+    double D = (double)(a[0] * a[4] - a[1] * a[3]);
+    D = D != 0 ? 1. / D : 0;
+    const double A11 = (double)a[4] * D;
+    const double A22 = (double)a[0] * D;
+    a[0] = (float)A11;
+    a[1] = (float)((double)a[1] * -D);
+    a[3] = (float)((double)a[3] * -D);
+    a[4] = (float)A22;
+    const float b1 = -a[0] * a[2] - a[1] * a[5];
+    const float b2 = -a[3] * a[2] - a[4] * a[5];
+    a[2] = b1;
+    a[5] = b2;
+    for (int k = 0; k < 6; ++k) inv[k] = a[k];
+}
+
 // Border modes for warp_affine beyond BORDER_CONSTANT.  The reference hands
 // every other mode to OpenCV (warp_affine.cpp:114-118 -> :48-50, recursing
 // forever without it); here they extend the reference's own naive sampler:

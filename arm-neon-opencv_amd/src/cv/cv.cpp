@@ -356,6 +356,102 @@ void warp_affine(const std::vector<Tensor>& src, std::vector<Tensor>& dst, const
     p.finish();
 }
 
+// ---- one frame, many crops (vacv_warp_affine_rois) -------------------------
+
+namespace {
+
+// waits for the stream before the staged operands of an early exit go away
+struct SyncOnExit {
+    hipStream_t s;
+    ~SyncOnExit() { (void)hipStreamSynchronize(s); }
+};
+
+// One launch for all crops: the frame and the matrices go to HBM once (host
+// operands through the pinned pool, device operands stay where they are), the
+// kernel writes the crops back to back into scratch, and each crop is copied
+// into its own dst tensor (placement of src).
+void warp_rois_into(const char* fn, const Tensor& src, std::vector<Tensor>& dst, const std::vector<Tensor>& M,
+                    VSize dsize, int flags, int borderMode, const VScalar& bv, const Stats* stats) {
+    if (src.empty()) fail(fn, "empty input tensor");
+    if (src.dtype != INT8 && src.dtype != FP32) fail(fn, "warp_affine takes INT8 or FP32");
+    if (src.layout != NHWC) fail(fn, "the crops of one frame take an NHWC frame");
+    if ((flags & ~(INTER_MAX | WARP_INVERSE_MAP)) || (flags & INTER_MAX) != INTER_LINEAR)
+        fail(fn, "only INTER_LINEAR (optionally | WARP_INVERSE_MAP) is supported for the crops of one frame");
+    if (borderMode < BORDER_CONSTANT || borderMode >= BORDER_TRANSPARENT) fail(fn, "unsupported border mode");
+    if (dsize.w < 1 || dsize.h < 1) fail(fn, "dsize must be positive");
+    if (M.empty()) fail(fn, "empty matrix list");
+    const size_t n = M.size();
+    const DType odt = stats ? FP32 : src.dtype;
+    const size_t roi_bytes = (size_t)dsize.w * dsize.h * src.c * dtype_size(odt);
+    if (n > 0x7FFFFFFFu) fail(fn, "too many matrices");
+    detail::Lease lease(detail::compute_device(src));
+    for (const Tensor& m : M) {
+        if (m.dtype != FP32 || m.size() != 6) fail(fn, "every M must be a 2x3 FP32 tensor");
+        if (m.on_device() && m.device() != lease.device()) fail(fn, "operands live on different devices");
+    }
+    if (src.on_device() && src.device() != lease.device()) fail(fn, "operands live on different devices");
+    const hipStream_t s = lease.stream();
+
+    Tensor mh(6, (int)n, 1, FP32, NCHW);  // the host matrices, contiguous, in pinned memory
+    if (!mh.data) fail(fn, "out of memory staging the matrices");
+    float* mp = static_cast<float*>(mh.data);
+    std::memset(mp, 0, n * 6 * sizeof(float));
+    for (size_t i = 0; i < n; ++i)
+        if (!M[i].on_device()) std::memcpy(mp + 6 * i, M[i].data, 6 * sizeof(float));
+    SyncOnExit guard{s};
+    float* dm = static_cast<float*>(lease.scratch(1, n * 6 * sizeof(float)));
+    detail::check_hip(fn, hipMemcpyAsync(dm, mp, n * 6 * sizeof(float), hipMemcpyHostToDevice, s));
+    for (size_t i = 0; i < n; ++i)
+        if (M[i].on_device())
+            detail::check_hip(fn, hipMemcpyAsync(dm + 6 * i, M[i].data, 6 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    void* sdev = src.data;
+    if (!src.on_device()) {
+        sdev = lease.scratch(0, src.len());
+        detail::check_hip(fn, hipMemcpyAsync(sdev, src.data, src.len(), hipMemcpyHostToDevice, s));
+    }
+    unsigned char* dout = static_cast<unsigned char*>(lease.scratch(2, n * roi_bytes));
+
+    const vacv_image sd = detail::describe(src, sdev);
+    vacv_image dd{};
+    dd.data = dout;
+    dd.n = (int)n;
+    dd.w = dsize.w;
+    dd.h = dsize.h;
+    dd.c = src.c;
+    dd.dtype = odt;
+    dd.layout = NHWC;
+    const double border[4] = {bv.v0, bv.v1, bv.v2, bv.v3};
+    if (stats)
+        detail::check(fn, vacv_warp_affine_rois_normalize(&sd, &dd, dm, nullptr, flags, borderMode, border, stats->m(),
+                                                          stats->s(), s));
+    else
+        detail::check(fn, vacv_warp_affine_rois(&sd, &dd, dm, nullptr, flags, borderMode, border, s));
+    dst.resize(n);
+    for (size_t i = 0; i < n; ++i) {
+        dst[i].create_on(src.device(), dsize.w, dsize.h, src.c, odt, NHWC);
+        if (roi_bytes > 0 && !dst[i].data) fail(fn, "out of memory creating the output tensor");
+        detail::check_hip(fn, hipMemcpyAsync(dst[i].data, dout + i * roi_bytes, roi_bytes,
+                                             dst[i].on_device() ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+    }
+    lease.sync(fn);
+}
+
+}  // namespace
+
+void warp_affine(const Tensor& src, std::vector<Tensor>& dst, const std::vector<Tensor>& M, VSize dsize, int flags,
+                 int borderMode, const VScalar& borderValue) {
+    warp_rois_into("va_cv::warp_affine", src, dst, M, dsize, flags, borderMode, borderValue, nullptr);
+}
+
+void warp_affine_normalize(const Tensor& src, std::vector<Tensor>& dst, const std::vector<Tensor>& M, VSize dsize,
+                           int flags, int borderMode, const VScalar& borderValue, const Tensor& mean,
+                           const Tensor& stddev) {
+    static const char* fn = "va_cv::warp_affine_normalize";
+    const Stats stats = read_stats(fn, mean, stddev, src.c, false);
+    if (!stats.m()) fail(fn, "the crops of one frame need mean and stddev (no per-image statistics)");
+    warp_rois_into(fn, src, dst, M, dsize, flags, borderMode, borderValue, &stats);
+}
+
 void cvt_color(const std::vector<Tensor>& src, std::vector<Tensor>& dst, int code) {
     static const char* fn = "va_cv::cvt_color";
     check_batch(fn, src, dst);

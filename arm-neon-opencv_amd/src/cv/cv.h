@@ -201,6 +201,23 @@ void resize_normalize(const std::vector<vision::Tensor>& src, std::vector<vision
 void warp_affine(const std::vector<vision::Tensor>& src, std::vector<vision::Tensor>& dst,
                  const vision::Tensor& M, VSize dsize, int flags = INTER_LINEAR,
                  int borderMode = BORDER_CONSTANT, const VScalar& borderValue = VScalar());
+/// One frame, M.size() crops, ONE kernel launch (the detection-pipeline shape
+/// of the (scale, rot, aux) overload above: one small upright crop per
+/// object, each with its own map).  dst[i] = warp_affine(src, M[i], dsize),
+/// byte for byte; src NHWC, INTER_LINEAR (optionally | WARP_INVERSE_MAP), every
+/// border mode but TRANSPARENT.  A host frame and host matrices are staged
+/// once through the pinned pool; device tensors stay where they are.  dst is
+/// resized to M.size(), each crop with the placement of src.
+void warp_affine(const vision::Tensor& src, std::vector<vision::Tensor>& dst,
+                 const std::vector<vision::Tensor>& M, VSize dsize, int flags = INTER_LINEAR,
+                 int borderMode = BORDER_CONSTANT, const VScalar& borderValue = VScalar());
+/// The same with the fused normalize (FP32 crops); mean and stddev are
+/// required (no per-image statistics for crops).
+void warp_affine_normalize(const vision::Tensor& src, std::vector<vision::Tensor>& dst,
+                           const std::vector<vision::Tensor>& M, VSize dsize, int flags = INTER_LINEAR,
+                           int borderMode = BORDER_CONSTANT, const VScalar& borderValue = VScalar(),
+                           const vision::Tensor& mean = vision::Tensor(),
+                           const vision::Tensor& stddev = vision::Tensor());
 void cvt_color(const std::vector<vision::Tensor>& src, std::vector<vision::Tensor>& dst, int code);
 void cvt_color_normalize(const std::vector<vision::Tensor>& src, std::vector<vision::Tensor>& dst, int code,
                          const vision::Tensor& mean = vision::Tensor(),

@@ -88,6 +88,9 @@ SIGNATURES = {
     "vacv_mean_stddev": ([_IMG, _P, _P, _P], _I),
     "vacv_resize_normalize": ([_IMG, _IMG, _I, _I, _FP, _FP, _P], _I),
     "vacv_warp_affine_normalize": ([_IMG, _IMG, _FP, _I, _I, _DP, _FP, _FP, _P], _I),
+    "vacv_warp_affine_rois": ([_IMG, _IMG, _P, _P, _I, _I, _DP, _P], _I),
+    "vacv_warp_affine_rois_normalize": ([_IMG, _IMG, _P, _P, _I, _I, _DP, _FP, _FP, _P], _I),
+    "vacv_invert_affine_device": ([_P, _P, _I, _P], _I),
     "vacv_cvt_color_normalize": ([_IMG, _IMG, _I, _FP, _FP, _P], _I),
     "vacv_cvt_color_resize": ([_IMG, _IMG, _I, _I, _I, _P], _I),
     "vacv_cvt_color_resize_normalize": ([_IMG, _IMG, _I, _I, _I, _FP, _FP, _P], _I),
@@ -109,8 +112,9 @@ TUNE = {"RESIZE_DIRECT": 0, "CUBIC_DIRECT": 1, "RESIZE_INTERLEAVE": 2, "DIRECT_X
 # include/vacv_hip.h VACV_ABI_VERSION: the tuning enum above and every
 # signature here are laid out for it (tests/test_abi.py checks the header).
 # Bumped with every change to a signature or to the tuning enum (3: round 6,
-# after round 5 added LANCZOS_KERNEL under version 2)
-ABI_VERSION = 3
+# after round 5 added LANCZOS_KERNEL under version 2; 4: the ROI warp entry
+# points and vacv_invert_affine_device)
+ABI_VERSION = 4
 
 _lib = None
 

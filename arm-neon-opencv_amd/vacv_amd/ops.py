@@ -243,6 +243,97 @@ def warp_affine_normalize(src: torch.Tensor, m, w: int, h: int, mean=None, std=N
     return _shape_back(out, src, layout)
 
 
+def _device_array(a, dtype: torch.dtype, device, what: str) -> torch.Tensor:
+    """A device tensor as it is (dense, of `dtype`, on `device`: anything else
+    raises, nothing is copied silently); numpy arrays and lists are moved to
+    the device for convenience."""
+    if not isinstance(a, torch.Tensor):
+        return torch.as_tensor(np.asarray(a), dtype=dtype).contiguous().to(device)
+    if a.device != device:
+        raise ValueError(f"{what} must live on {device}, not {a.device}")
+    if a.dtype != dtype:
+        raise ValueError(f"{what} must be {dtype}, not {a.dtype}")
+    if not a.is_contiguous():
+        raise ValueError(f"{what} must be contiguous")
+    return a
+
+
+def _rois_args(src: torch.Tensor, ms, src_index):
+    s4 = _as4d(src, NHWC)
+    ms = _device_array(ms, torch.float32, s4.device, "ms")
+    if not (ms.dim() == 2 and ms.shape[1] == 6) and not (ms.dim() == 3 and tuple(ms.shape[1:]) == (2, 3)):
+        raise ValueError(f"ms must have shape (n, 6) or (n, 2, 3), got {tuple(ms.shape)}")
+    n = ms.shape[0]
+    if n < 1:
+        raise ValueError("ms holds no matrix")
+    if src_index is not None:
+        src_index = _device_array(src_index, torch.int32, s4.device, "src_index")
+        if tuple(src_index.shape) != (n,):
+            raise ValueError(f"src_index must have shape ({n},), got {tuple(src_index.shape)}")
+    elif s4.shape[0] not in (1, n):
+        raise ValueError(f"without src_index, src must hold 1 or {n} images, not {s4.shape[0]}")
+    return s4, ms, src_index, n
+
+
+def warp_affine_rois(src: torch.Tensor, ms, w: int, h: int, src_index=None, flags: int = INTER_LINEAR,
+                     border_mode: int = BORDER_CONSTANT, border_value=(0, 0, 0, 0), out=None,
+                     stream=None) -> torch.Tensor:
+    """Many crops in one launch: out[i] = warp_affine(src[src_index[i]], ms[i], w, h).
+    src: NHWC frames (n, h, w, c) or one (h, w, c) / (h, w) frame.  ms: (n, 6)
+    or (n, 2, 3) float32 device tensor; src_index: (n,) int32 device tensor, or
+    None (one frame for all, or frame i for ROI i).  Both are read by the
+    kernel when it runs on `stream`, not by this call.  Returns (n, h, w, c)."""
+    s4, ms, src_index, n = _rois_args(src, ms, src_index)
+    if out is None:
+        out = torch.empty((n, h, w, s4.shape[3]), dtype=src.dtype, device=src.device)
+    bv, bp = _dptr((list(border_value) + [0, 0, 0, 0])[:4])  # the C side reads four
+    check("vacv_warp_affine_rois", L.load().vacv_warp_affine_rois(
+        ctypes.byref(describe(s4, NHWC)), ctypes.byref(describe(out, NHWC)), ms.data_ptr(),
+        src_index.data_ptr() if src_index is not None else None, flags, border_mode, bp, _stream(stream)))
+    return out
+
+
+def warp_affine_rois_normalize(src: torch.Tensor, ms, w: int, h: int, mean, std, src_index=None,
+                               out_layout: int = NHWC, flags: int = INTER_LINEAR,
+                               border_mode: int = BORDER_CONSTANT, border_value=(0, 0, 0, 0), out=None,
+                               stream=None) -> torch.Tensor:
+    """warp_affine_rois with the fused normalize: fp32 (n, h, w, c), or planar
+    (n, c, h, w) with out_layout=NCHW (c = 3 or 1), the model-input layout."""
+    s4, ms, src_index, n = _rois_args(src, ms, src_index)
+    c = s4.shape[3]
+    if mean is None or std is None:
+        raise ValueError("warp_affine_rois_normalize needs mean and stddev (no per-image statistics for ROIs)")
+    if out is None:
+        out = torch.empty((n, h, w, c) if out_layout == NHWC else (n, c, h, w), dtype=torch.float32,
+                          device=src.device)
+    bv, bp = _dptr((list(border_value) + [0, 0, 0, 0])[:4])  # the C side reads four
+    (ma, meanp), (sa, stdp) = _meanstd(mean, std, c)
+    check("vacv_warp_affine_rois_normalize", L.load().vacv_warp_affine_rois_normalize(
+        ctypes.byref(describe(s4, NHWC)), ctypes.byref(describe(out, out_layout)), ms.data_ptr(),
+        src_index.data_ptr() if src_index is not None else None, flags, border_mode, bp, meanp, stdp,
+        _stream(stream)))
+    return out
+
+
+def invert_affine_device(ms: torch.Tensor, out=None, stream=None) -> torch.Tensor:
+    """vacv_invert_affine of every map of a float32 device tensor (n, 6) or
+    (n, 2, 3), on the device (bit-identical to the host function)."""
+    if not isinstance(ms, torch.Tensor) or not ms.is_cuda:
+        raise ValueError("invert_affine_device takes a device tensor (invert_affine is the host function)")
+    ms = _device_array(ms, torch.float32, ms.device, "ms")
+    if ms.numel() % 6:
+        raise ValueError(f"ms must hold 2x3 maps, got shape {tuple(ms.shape)}")
+    if out is None:
+        out = torch.empty_like(ms)
+    else:
+        out = _device_array(out, torch.float32, ms.device, "out")
+        if out.shape != ms.shape:
+            raise ValueError("out must have the shape of ms")
+    check("vacv_invert_affine_device", L.load().vacv_invert_affine_device(ms.data_ptr(), out.data_ptr(),
+                                                                          ms.numel() // 6, _stream(stream)))
+    return out
+
+
 # ---------------------------------------------------------------------------
 # colour
 

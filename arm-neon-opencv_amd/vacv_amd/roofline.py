@@ -90,3 +90,63 @@ def yuv_resize_bytes(w_in: int, h_in: int, w_out: int, h_out: int, out_esize: in
     rows = set(i[w0 != 0].tolist()) | set((i[w1 != 0] + 1).tolist())
     chroma = {r >> 1 for r in rows}
     return (len(rows) + len(chroma)) * w_in + w_out * h_out * 3 * out_esize
+
+
+def _clip_polygon(poly, w: float, h: float):
+    """Sutherland-Hodgman: the convex polygon `poly` cut to [0, w] x [0, h]."""
+    def cut(pts, inside, cross):
+        out = []
+        for i, p in enumerate(pts):
+            q = pts[(i + 1) % len(pts)]
+            if inside(p):
+                out.append(p)
+                if not inside(q):
+                    out.append(cross(p, q))
+            elif inside(q):
+                out.append(cross(p, q))
+        return out
+
+    def at_x(x0):
+        return lambda p, q: (x0, p[1] + (q[1] - p[1]) * (x0 - p[0]) / (q[0] - p[0]))
+
+    def at_y(y0):
+        return lambda p, q: (p[0] + (q[0] - p[0]) * (y0 - p[1]) / (q[1] - p[1]), y0)
+
+    for inside, cross in ((lambda p: p[0] >= 0, at_x(0.0)), (lambda p: p[0] <= w, at_x(float(w))),
+                          (lambda p: p[1] >= 0, at_y(0.0)), (lambda p: p[1] <= h, at_y(float(h)))):
+        if not poly:
+            break
+        poly = cut(poly, inside, cross)
+    return poly
+
+
+def warp_rois_bytes(w_in: int, h_in: int, c: int, w_out: int, h_out: int, ms, in_esize: int = 1,
+                    out_esize: int = 1, inverse_map: bool = False) -> int:
+    """B_alg of vacv_warp_affine_rois: the output bytes of every ROI plus the
+    bytes of each ROI's source parallelogram -- the image of the output
+    rectangle [0, w_out] x [0, h_out] under the dst -> src map -- clipped to
+    the frame [0, w_in] x [0, h_in] (its area rounded to whole pixels).  From
+    shapes and matrices alone, on the host, in float64; a singular or
+    non-finite map reads nothing.  Source pixels that two ROIs share are
+    counted for both: each ROI is its own launch-independent piece of work."""
+    ms = np.asarray(ms, dtype=np.float64).reshape(-1, 6)
+    total = ms.shape[0] * w_out * h_out * c * out_esize
+    for m in ms:
+        if not np.all(np.isfinite(m)):
+            continue
+        if inverse_map:
+            inv = m
+        else:
+            det = m[0] * m[4] - m[1] * m[3]
+            if det == 0:
+                continue
+            a, b, d, e = m[4] / det, -m[1] / det, -m[3] / det, m[0] / det
+            inv = np.array([a, b, -a * m[2] - b * m[5], d, e, -d * m[2] - e * m[5]])
+        corners = [(inv[0] * x + inv[1] * y + inv[2], inv[3] * x + inv[4] * y + inv[5])
+                   for x, y in ((0, 0), (w_out, 0), (w_out, h_out), (0, h_out))]
+        poly = _clip_polygon(corners, w_in, h_in)
+        if len(poly) < 3:
+            continue
+        area = 0.5 * abs(sum(p[0] * q[1] - q[0] * p[1] for p, q in zip(poly, poly[1:] + poly[:1])))
+        total += int(round(area)) * c * in_esize
+    return int(total)

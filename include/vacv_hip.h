@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define VACV_ABI_VERSION 3
+#define VACV_ABI_VERSION 4
 #define VACV_MAX_CHANNELS 16
 
 typedef enum vacv_status {
@@ -264,6 +264,52 @@ int vacv_resize_normalize(const vacv_image* src, const vacv_image* dst, int inte
 int vacv_warp_affine_normalize(const vacv_image* src, const vacv_image* dst, const float m[6],
                                int flags, int border_mode, const double border_value[4],
                                const float* mean, const float* stddev, void* stream);
+
+/* Many crops in one launch (the detection-pipeline shape of the reference's
+ * warp_affine(src, dst, scale, rot, dsize, aux) overload: one small upright
+ * crop per detected object, each with its own map).
+ * dst image i = warp_affine of src image src_index[i] under the 2x3 map m[i].
+ * src: `src->n` frames, NHWC, c = 1..4, INT8 or FP32, pitched or dense, any
+ *      base alignment (NCHW: UNSUPPORTED).
+ * dst: `dst->n` = number of ROIs, all dst->w x dst->h, dtype and layout of
+ *      src; ROIs may be pitched (row and batch pitch).
+ * m:         DEVICE array [dst->n][6] float, row-major.  Forward maps, or
+ *            dst -> src maps with flags | VACV_WARP_INVERSE_MAP.
+ * src_index: DEVICE array [dst->n] int32, or NULL.
+ *            NULL needs src->n == 1 (every ROI reads frame 0)
+ *            or src->n == dst->n (ROI i reads frame i).
+ *            Any other NULL case is VACV_ERR_INVALID_ARG.
+ * Both arrays are read by the kernel, on `stream`, at execution time: the
+ * call copies nothing between host and device, allocates nothing and never
+ * synchronizes, and host code never dereferences them.
+ * flags: INTER_LINEAR, optionally | VACV_WARP_INVERSE_MAP (else UNSUPPORTED).
+ * border_mode: CONSTANT, REPLICATE, REFLECT, WRAP, REFLECT_101 as
+ * vacv_warp_affine defines them (TRANSPARENT: UNSUPPORTED).
+ * ROI i is byte-identical to what vacv_warp_affine writes for the single
+ * image src[src_index[i]] with the host matrix m[i]; bytes of the dst
+ * allocation outside the ROI rectangles are never written.
+ * Device-supplied values cannot fault: a src_index[i] outside [0, src->n)
+ * gives a ROI filled with border_value (in every border mode) and reads no
+ * source byte; a zero-determinant map inverts to all zeros as
+ * vacv_invert_affine defines; a non-finite map under BORDER_CONSTANT gives an
+ * all-border ROI; every sampler read is range-checked against the indexed
+ * frame by the hardware. */
+int vacv_warp_affine_rois(const vacv_image* src, const vacv_image* dst, const float* m,
+                          const int32_t* src_index, int flags, int border_mode,
+                          const double border_value[4], void* stream);
+/* The same, normalized: dst is FP32, NHWC or NCHW (planar output for c = 3
+ * and c = 1; other channel counts: UNSUPPORTED), pitched or dense (row, plane
+ * and batch pitch).  mean / stddev: host arrays of c floats, both required
+ * (one NULL: INVALID_ARG; both NULL, per-image statistics: UNSUPPORTED).
+ * ROI i is byte-identical to vacv_warp_affine_normalize on that image,
+ * followed by vacv_change_layout when dst is NCHW. */
+int vacv_warp_affine_rois_normalize(const vacv_image* src, const vacv_image* dst, const float* m,
+                                    const int32_t* src_index, int flags, int border_mode,
+                                    const double border_value[4],
+                                    const float* mean, const float* stddev, void* stream);
+/* inv[i] = vacv_invert_affine(m[i]) for n maps, bit for bit.  DEVICE in,
+ * DEVICE out, queued on `stream`. */
+int vacv_invert_affine_device(const float* m, float* inv, int n, void* stream);
 
 /* cvt_color then normalize (the cfg3 pipeline), dst (w,h,3) FP32 NHWC. */
 int vacv_cvt_color_normalize(const vacv_image* src, const vacv_image* dst, int code,

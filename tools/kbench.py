@@ -25,6 +25,12 @@ def main():
     ap.add_argument("--sweep", default="",
                     help="kernel-variant knobs (VACV_TUNE_*, vacv_set_tuning) to sweep, "
                          "e.g. 'DIRECT_ALIGN=0,1;RESIZE_WORK=2,4'")
+    ap.add_argument("--compare", action="store_true",
+                    help="--op warp_rois: time each one-call case against the same crops as a loop of single "
+                         "calls (vacv_warp_affine; vacv_warp_affine_normalize + one vacv_change_layout), alternating")
+    ap.add_argument("--baseline-lib", default="",
+                    help="--compare: libvacv_hip.so of another build (e.g. the parent commit's) to run the loop on; "
+                         "default: this build's own single-call entry points")
     a = ap.parse_args()
     import torch
     import vacv_amd
@@ -173,8 +179,56 @@ def main():
         src = frames(n, 360, 640)
         cases["hwc_to_chw_640x360_u8"] = (lambda src=src: ops.change_layout(src, vacv_amd.NCHW),
                                           n * 640 * 360 * 6, n * 640 * 360)
+    loops = {}
+    if a.op in ("warp_rois", "all"):
+        # many small crops, each with its own matrix, in ONE launch
+        # (vacv_warp_affine_rois): seeded geometry -- rotation uniform in +-30
+        # degrees, a source footprint of ~250 px per side, centres anywhere in
+        # the frame (so some crops hang partly off it)
+        import numpy as np
+        from vacv_amd.roofline import warp_rois_bytes
+        rng = np.random.default_rng(20261019)
+
+        def roi_maps(n, fw, fh, wo, ho, foot=250.0):
+            ms = np.zeros((n, 6), np.float32)
+            for i in range(n):
+                ang, s = np.deg2rad(rng.uniform(-30.0, 30.0)), max(wo, ho) / foot
+                cx, cy = rng.uniform(0, fw), rng.uniform(0, fh)
+                ca, sa = s * np.cos(ang), s * np.sin(ang)
+                ms[i] = [ca, sa, wo / 2 - ca * cx - sa * cy, -sa, ca, ho / 2 + sa * cx - ca * cy]
+            return ms
+
+        src = frames(8, 1080, 1920)
+        ms = roi_maps(256, 1920, 1080, 112, 112)
+        idx = np.arange(256, dtype=np.int32) % 8
+        dms, didx = torch.from_numpy(ms).to(dev), torch.from_numpy(idx).to(dev)
+        o = torch.empty((256, 112, 112, 3), dtype=torch.uint8, device=dev)
+        cases["warp_rois_1080p_256x112_u8"] = (
+            lambda src=src, dms=dms, didx=didx, o=o: ops.warp_affine_rois(src, dms, 112, 112, src_index=didx, out=o),
+            warp_rois_bytes(1920, 1080, 3, 112, 112, ms), 256 * 112 * 112)
+        loops["warp_rois_1080p_256x112_u8"] = dict(src=src, ms=ms, idx=idx, out=torch.empty_like(o), norm=False)
+        of = torch.empty((256, 3, 112, 112), dtype=torch.float32, device=dev)
+        cases["warp_rois_normalize_1080p_256x112_chw"] = (
+            lambda src=src, dms=dms, didx=didx, of=of: ops.warp_affine_rois_normalize(
+                src, dms, 112, 112, MEAN, STD, src_index=didx, out_layout=vacv_amd.NCHW, out=of),
+            warp_rois_bytes(1920, 1080, 3, 112, 112, ms, out_esize=4), 256 * 112 * 112)
+        loops["warp_rois_normalize_1080p_256x112_chw"] = dict(src=src, ms=ms, idx=idx, out=torch.empty_like(of),
+                                                              norm=True)
+        # the reference harness's crop size: 64 crops of one 1280 x 720 frame
+        src7 = frames(1, 720, 1280)
+        ms7 = roi_maps(64, 1280, 720, 140, 210)
+        dms7 = torch.from_numpy(ms7).to(dev)
+        o7 = torch.empty((64, 210, 140, 3), dtype=torch.uint8, device=dev)
+        cases["warp_rois_720p_64x140x210_u8"] = (
+            lambda src7=src7, dms7=dms7, o7=o7: ops.warp_affine_rois(src7, dms7, 140, 210, out=o7),
+            warp_rois_bytes(1280, 720, 3, 140, 210, ms7), 64 * 140 * 210)
+        loops["warp_rois_720p_64x140x210_u8"] = dict(src=src7, ms=ms7, idx=np.zeros(64, np.int32),
+                                                     out=torch.empty_like(o7), norm=False)
     if a.only:
         cases = {k: v for k, v in cases.items() if a.only in k}
+    if a.compare:
+        compare_with_loops({k: v for k, v in cases.items() if k in loops}, loops, a.baseline_lib, a.iters)
+        return
     import itertools
     knobs = [kv.split("=", 1) for kv in a.sweep.split(";") if kv]
     combos = list(itertools.product(*[[(k, v) for v in vals.split(",")] for k, vals in knobs])) or [()]
@@ -187,6 +241,75 @@ def main():
             ops.set_tuning(k, int(v))
         tag = " ".join(f"{k}={v}" for k, v in combo)
         run_cases(cases, a.iters, tag)
+
+
+def compare_with_loops(cases, loops, baseline_lib, iters):
+    """One call for all crops against a loop of single calls, per case: both
+    timed end to end with a host clock around a synchronised stream (the
+    loop's time is mostly launches and host plans, which device events would
+    not see), alternating, after warm-up.  The loop's descriptors, matrices and
+    ctypes references are built beforehand, so what is timed is the library."""
+    import ctypes
+    import time
+
+    import torch
+    import vacv_amd
+    from vacv_amd import _lib as L, ops
+    if baseline_lib:
+        # another build by its own handle: only entry points both builds share
+        base = ctypes.CDLL(str(Path(baseline_lib).resolve()))
+        for fname in ("vacv_warp_affine", "vacv_warp_affine_normalize", "vacv_change_layout", "vacv_abi_version"):
+            getattr(base, fname).argtypes, getattr(base, fname).restype = L.SIGNATURES[fname]
+        tag = f"{baseline_lib} (ABI {base.vacv_abi_version()})"
+    else:
+        base, tag = L.load(), "this build"
+    stream = ops._stream()
+    bv = (ctypes.c_double * 4)(0, 0, 0, 0)
+    mean, std = (ctypes.c_float * 3)(*MEAN), (ctypes.c_float * 3)(*STD)
+    for name, (fn, nbytes, px) in cases.items():
+        lp = loops[name]
+        src, ms, idx, out, norm = lp["src"], lp["ms"], lp["idx"], lp["out"], lp["norm"]
+        n = len(ms)
+        ho, wo = (out.shape[2], out.shape[3]) if norm else (out.shape[1], out.shape[2])
+        tmp = torch.empty((n, ho, wo, 3), dtype=torch.float32, device=out.device) if norm else out
+        keep = [ops.describe(src[i:i + 1]) for i in range(src.shape[0])] + [ops.describe(tmp[i:i + 1]) for i in range(n)]
+        fd = [ctypes.byref(d) for d in keep[:src.shape[0]]]
+        dd = [ctypes.byref(d) for d in keep[src.shape[0]:]]
+        mp = [(ctypes.c_float * 6)(*[float(v) for v in m]) for m in ms]
+        whole_tmp, whole_out = ops.describe(tmp), ops.describe(out, vacv_amd.NCHW if norm else vacv_amd.NHWC)
+        frame_of = [int(k) for k in idx]
+
+        def loop():
+            if norm:
+                for i in range(n):
+                    assert base.vacv_warp_affine_normalize(fd[frame_of[i]], dd[i], mp[i], 1, 0, bv, mean, std, stream) == 0
+                assert base.vacv_change_layout(ctypes.byref(whole_tmp), ctypes.byref(whole_out), stream) == 0
+            else:
+                for i in range(n):
+                    assert base.vacv_warp_affine(fd[frame_of[i]], dd[i], mp[i], 1, 0, bv, stream) == 0
+
+        def timed(f):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            f()
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) * 1e3
+
+        for _ in range(5):
+            loop()
+            one = fn()
+        torch.cuda.synchronize()
+        same = bool(torch.equal(one, out))  # both legs compute the same crops
+        t_loop, t_one = [], []
+        for _ in range(iters):
+            t_loop.append(timed(loop))
+            t_one.append(timed(fn))
+        ml, mo = sorted(t_loop)[iters // 2], sorted(t_one)[iters // 2]
+        print(json.dumps({"case": name, "rois": n, "baseline": tag, "loop_ms_median": round(ml, 4),
+                          "loop_ms_min": round(min(t_loop), 4), "one_call_ms_median": round(mo, 4),
+                          "one_call_ms_min": round(min(t_one), 4), "loop_over_one_call": round(ml / mo, 2),
+                          "alg_bytes": int(nbytes), "one_call_alg_GBps": round(nbytes / mo / 1e6, 1),
+                          "outputs_equal": same, "clock": "host, stream synchronised"}), flush=True)
 
 
 def run_cases(cases, iters, tag):
