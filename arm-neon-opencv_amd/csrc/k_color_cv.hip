@@ -234,9 +234,7 @@ __global__ void __launch_bounds__(256) yuv420_cv8x_kernel(CvColorLaunch L, int u
 #pragma unroll
             for (int k = 0; k < 3; ++k) *reinterpret_cast<u32x2*>(xw + 6 * lane + 2 * k) = u32x2{w[2 * k], w[2 * k + 1]};
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
         unsigned char* o = L.dst + (int64_t)img * L.dst_img + (int64_t)(2 * by + r) * L.dst_row + (int64_t)blk * 64 * 8 * DCN;
 #pragma unroll
         for (int j = 0; j < (2 * DCN + 3) / 4; ++j) {  // 16-byte chunks per lane, rounded up: BGRA 2, BGR 2
@@ -248,9 +246,7 @@ __global__ void __launch_bounds__(256) yuv420_cv8x_kernel(CvColorLaunch L, int u
         }
         if (DCN == 3 && (nl & 1) && lane == 0)  // an odd lane count leaves 8 bytes
             *reinterpret_cast<u32x2*>(o + 16 * nck) = *reinterpret_cast<const u32x2*>(xw + 4 * nck);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();  // the next row reuses the slice
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();  // the next row reuses the slice
     }
 }
 
@@ -365,9 +361,7 @@ __global__ void __launch_bounds__(256) gray_x_kernel(CvColorLaunch L, int upr, i
 #pragma unroll
     for (int k = 0; k < OW / 4; ++k)
         *reinterpret_cast<u32x4*>(xw + OW * lane + 4 * k) = u32x4{w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]};
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     const int nck = nl * OW / 4;  // 16-byte chunks of the wave's output run
 #pragma unroll
     for (int j = 0; j < OW / 4; ++j) {

@@ -224,9 +224,7 @@ cubic_direct_kernel(ResizeLaunch L, int blocks_per_plane) {
     // Lanes read bytes other lanes of the wave wrote to xch: order those
     // writes before the reads (the SUMS instance's __syncthreads already did).
     if (!SUMS) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
     }
     unsigned char* dp = const_cast<unsigned char*>(L.dst.base) + (int64_t)img * L.dst.img_pitch +
                         (int64_t)plane * L.dst.plane_pitch;
@@ -238,28 +236,7 @@ cubic_direct_kernel(ResizeLaunch L, int blocks_per_plane) {
     const uint32_t vbytes = (uint32_t)npx * CC * 4u;
     const uint32_t b0 = (uint32_t)p0 * CC * 4u;
     const unsigned char* xs = reinterpret_cast<const unsigned char*>(xch[threadIdx.y]);
-    if (chunked) {
-        for (uint32_t c = lane; c * 16 < vbytes; c += 64) {
-            const uint32_t b = b0 + 16 * c;
-            uint32_t off = b;
-            if (!dense) {
-                const uint32_t r = b / out_row;
-                off = r * rowp + (b - r * out_row);
-            }
-            if (c * 16 + 16 <= vbytes) {
-                __builtin_nontemporal_store(*reinterpret_cast<const u32x4*>(xs + 16 * c),
-                                            reinterpret_cast<u32x4*>(dp + off));
-            } else {
-                for (uint32_t e = c * 16; e < vbytes; ++e) dp[off + (e - c * 16)] = xs[e];
-            }
-        }
-    } else {
-        for (uint32_t e = lane; e < vbytes; e += 64) {
-            const uint32_t b = b0 + e;
-            const uint32_t r = b / out_row;
-            dp[(int64_t)r * rowp + (b - r * out_row)] = xs[e];
-        }
-    }
+    store_range_from_lds(dp, xs, b0, vbytes, out_row, rowp, dense, chunked, lane);
 }
 
 // ---- the column kernel's statistics: fixed-point integer sums -----------------
@@ -418,9 +395,7 @@ cubic_cols_kernel(ResizeLaunch L, int col_blocks, int plane_tasks, int blocks_pe
                 }
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
         // ---- LDS -> HBM: nrow rows of ncol * CC floats (the host checked the
         // destination's 16-byte alignment) ----------------------------------------
         unsigned char* dp = const_cast<unsigned char*>(L.dst.base) + (int64_t)img * L.dst.img_pitch +

@@ -99,6 +99,7 @@ __device__ __forceinline__ void lz_h_u8(const uint32_t* wv, const uint32_t (&cp)
             const int e0 = lz_pos<SH>(2 * m) * CC + k, e1 = lz_pos<SH>(2 * m + 1) * CC + k;
             const int q0 = e0 >> 2;
             const uint32_t lo = wv[q0], hi = q0 + 1 < NW ? wv[q0 + 1] : 0u;
+            // not tap_pair: two arbitrary window bytes (SH taps apart), not bytes k and CC + k
             const uint32_t sel = (uint32_t)(e0 - 4 * q0) | (0x0Cu << 8) | ((uint32_t)(e1 - 4 * q0) << 16) | (0x0Cu << 24);
             const uint32_t pr = __builtin_amdgcn_perm(hi, lo, sel);
             v = __builtin_amdgcn_sdot2(__builtin_bit_cast(sh2, pr), __builtin_bit_cast(sh2, cp[m]), v, false);
@@ -615,14 +616,10 @@ lanczos_u8_kernel(LanczosLaunch L, int strips, int bands, int band_rows,
     // NI > 0: the run through the wave's slice, then this lane's window
     auto hrow_run = [&](const u32x4 (&t)[NI > 0 ? NI : 1], int (&hv)[CC]) {
         uint32_t* xw = xs[NI > 0 ? wave : 0];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();  // the previous row's window reads are done
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();  // the previous row's window reads are done
 #pragma unroll
         for (int i = 0; i < (NI > 0 ? NI : 1); ++i) *reinterpret_cast<u32x4*>(xw + 4 * (64 * i + lane)) = t[i];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
         uint32_t d[ND];
         const uint32_t* wp = xw + (wofs >> 2);
 #pragma unroll

@@ -84,9 +84,7 @@ __global__ void __launch_bounds__(kBlock) match_corr_u8_kernel(MatchLaunch M) {
             }
             row[d] = v;
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
         // lane's outputs start at byte 4*lane*CN = dword lane*CN
         const uint32_t* rp = row + lane * CN;
         const uint32_t* tp = tpl + yy * K4;
@@ -109,9 +107,7 @@ __global__ void __launch_bounds__(kBlock) match_corr_u8_kernel(MatchLaunch M) {
         }
 #pragma unroll
         for (int o = 0; o < kOutPerLane; ++o) acc[o] += a32[o];  // a row: <= 255^2 * K < 2^32
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
     }
     float* out = reinterpret_cast<float*>(M.res + (int64_t)img * M.res_pitch + (int64_t)r * M.res_row);
 #pragma unroll
@@ -144,9 +140,7 @@ __global__ void __launch_bounds__(kBlock) match_corr_f32_kernel(MatchLaunch M) {
     for (int yy = 0; yy < h; ++yy) {
         const float* ir = reinterpret_cast<const float*>(ib + (int64_t)(r + yy) * M.img_row);
         for (int e = lane; e < span; e += 64) row[e] = ebase + e < row_el ? ir[ebase + e] : 0.f;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
         const float* rp = row + 4 * lane * CN;
         const float* tp = tpl + yy * K;
         for (int k = 0; k < K; ++k) {
@@ -154,9 +148,7 @@ __global__ void __launch_bounds__(kBlock) match_corr_f32_kernel(MatchLaunch M) {
 #pragma unroll
             for (int o = 0; o < kOutPerLane; ++o) acc[o] += t * (double)rp[o * CN + k];
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
     }
     float* out = reinterpret_cast<float*>(M.res + (int64_t)img * M.res_pitch + (int64_t)r * M.res_row);
 #pragma unroll

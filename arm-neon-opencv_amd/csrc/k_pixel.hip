@@ -278,16 +278,12 @@ __global__ void __launch_bounds__(kBlock) color_kernel(ColorLaunch L) {
                 for (int b = 0; b < 3; ++b)
                     w[lane * 3 + b] = u32x4{__float_as_uint(out[4 * b]), __float_as_uint(out[4 * b + 1]),
                                             __float_as_uint(out[4 * b + 2]), __float_as_uint(out[4 * b + 3])};
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                wave_lds_sync();
 #pragma unroll
                 for (int b = 0; b < 3; ++b) {
                     __builtin_nontemporal_store(w[b * 64 + lane], reinterpret_cast<u32x4*>(wbase) + b * 64 + lane);
                 }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();  // the next row reuses the exchange buffer
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                wave_lds_sync();  // the next row reuses the exchange buffer
                 continue;
             }
         }
@@ -671,9 +667,7 @@ __global__ void __launch_bounds__(kBlock) nearest_wave_kernel(ResizeLaunch L, in
     }
     unsigned char* lb = reinterpret_cast<unsigned char*>(slice);
     for (int i = (n16 << 4) + lane; i < row_bytes; i += 64) lb[i] = sp[i];
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     const TIn* row = reinterpret_cast<const TIn*>(lb);
 
     ChanNorm cn[CC] = {};
@@ -948,7 +942,7 @@ __global__ void __launch_bounds__(kBlock) area_u8_colsum_kernel(ResizeLaunch L, 
 // above alternated a load phase and an LDS/output phase per workgroup that
 // never overlapped (diagnosis builds at 2x2: loads alone 0.263 ms, the rest
 // alone 0.250, both 0.519).  Integer sums: bit-identical to it.
-// cache policy of the unit kernel's stores (A/B builds: EXTRA=-D0=n)
+// The unit kernel's stores use the default cache policy (aux 0), fixed.
 template <int AX, int CC>
 struct AreaUnit {
     static constexpr int gcd(int a, int b) { return b == 0 ? a : gcd(b, a % b); }
@@ -1042,9 +1036,7 @@ __global__ void __launch_bounds__(kBlock) area_u8_unit_kernel(ResizeLaunch L, in
         *reinterpret_cast<uint4*>(xw + 8 * q) = make_uint4(ev[4 * c], ev[4 * c + 1], ev[4 * c + 2], ev[4 * c + 3]);
         *reinterpret_cast<uint4*>(xw + 8 * q + 4) = make_uint4(od[4 * c], od[4 * c + 1], od[4 * c + 2], od[4 * c + 3]);
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
         const int q = NCH * lane + c;
@@ -1096,14 +1088,10 @@ __global__ void __launch_bounds__(kBlock) area_u8_unit_kernel(ResizeLaunch L, in
     // unit's bytes apart)
     if (packed && wu0 + 64 <= total) {  // uniform
         constexpr int NW = OUT == kOutSame ? OB / 4 : OB;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();  // every lane has read its column sums back
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();  // every lane has read its column sums back
 #pragma unroll
         for (int i = 0; i < NW; ++i) xw[NW * lane + i] = outw[i];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
         u32x4* o = reinterpret_cast<u32x4*>(const_cast<unsigned char*>(L.dst.base) + (int64_t)wu0 * OB * ES);
 #pragma unroll
         for (int j = 0; j < (NW + 3) / 4; ++j) {
@@ -1422,18 +1410,14 @@ __global__ void __launch_bounds__(kBlock) area_lane_kernel(ResizeLaunch L, int b
                     *reinterpret_cast<u32x4*>(&xs[wv][1][4 * q]) = u32x4{cod[i][0], cod[i][1], cod[i][2], cod[i][3]};
                 }
             }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_sync();
 #pragma unroll
             for (int q = 0; q < NW; ++q) {
                 ev[q] = xs[wv][0][NW * lane + q];
                 od[q] = xs[wv][1][NW * lane + q];
             }
             emit(y);
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();  // the next row reuses the slice
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_sync();  // the next row reuses the slice
         }
         return;
     }

@@ -93,27 +93,18 @@ struct Sampler<kLinearFixed, CC, uint8_t, MODE> {
         // [0, 2048]: xw = {a0, a1} is a u16 pair, the row sums tl*a0 + tr*a1
         // (< 2^24) are one packed dot product (v_dot2_u32_u16), and every
         // further product is an exact full-rate 24-bit multiply.
-        typedef unsigned short us2 __attribute__((ext_vector_type(2)));
         const us2 wx = __builtin_bit_cast(us2, xw);
         const unsigned char* pa = rows + r.rb[0] + off;
         const unsigned char* pb = rows + r.rb[1] + off;
         const uint32_t top = (uint32_t)pa[0] | ((uint32_t)pa[CC] << 16);
-        uint32_t bot = 0;
-        if (TWO) bot = (uint32_t)pb[0] | ((uint32_t)pb[CC] << 16);
-        const uint32_t ht = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, top), wx, 0u, false);
-        const uint32_t hb = TWO ? __builtin_amdgcn_udot2(__builtin_bit_cast(us2, bot), wx, 0u, false) : 0u;
         const uint32_t wA = (uint32_t)r.w[0], wB = (uint32_t)r.w[1];
-        if (MODE == VACV_LINEAR_REFERENCE) {
-            // resize_naive.cpp:61-64: (Sum S*wx*wy) >> 22, stored as a byte;
-            // (tl*a0 + tr*a1)*wA + (bl*a0 + br*a1)*wB is the same int32 value
-            // (all terms >= 0, total <= 255*2049^2 < 2^31)
-            if (TWO) return (int)(((__umul24(ht, wA) + __umul24(hb, wB)) >> 22) & 0xFF);
-            return (int)((__umul24(ht, wA) >> 22) & 0xFF);
-        }
+        // resize_naive.cpp:61-64: (Sum S*wx*wy) >> 22, stored as a byte;
         // resize_neon.cpp:103,122-123 (int16 rows), :150-167 (vertical)
-        const int h0 = (int)(short)(ht >> 4);
-        const int h1 = (int)(short)(hb >> 4);
-        return clamp_u8((((h0 * (int)wA) >> 16) + ((h1 * (int)wB) >> 16) + 2) >> 2);
+        if (TWO) return blend_fixed<MODE>(top, (uint32_t)pb[0] | ((uint32_t)pb[CC] << 16), wx, wA, wB);
+        // one row: written out, blend_fixed would add the second dot product back
+        const uint32_t ht = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, top), wx, 0u, false);
+        if (MODE == VACV_LINEAR_REFERENCE) return (int)((__umul24(ht, wA) >> 22) & 0xFF);
+        return clamp_u8(((((int)(short)(ht >> 4) * (int)wA) >> 16) + 2) >> 2);
     }
 };
 

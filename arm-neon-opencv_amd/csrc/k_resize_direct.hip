@@ -71,8 +71,7 @@ resize_direct_kernel(ResizeLaunch L, int blocks_per_plane, int total, int xcd) {
     // xcd: workgroup b runs on XCD b % 8; give each XCD one contiguous eighth
     // of the work so source rows shared by neighbouring workgroups (two-tap
     // rows) are fetched into one L2 only
-    const int per_xcd = (total + 7) >> 3;
-    const int id = xcd ? (int)(blockIdx.x & 7) * per_xcd + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
+    const int id = xcd ? xcd_block_id(total) : (int)blockIdx.x;
     if (id >= total) return;  // uniform
     const int pidx = id / blocks_per_plane;  // image * planes + plane
     const int blk = id - pidx * blocks_per_plane;
@@ -169,19 +168,12 @@ resize_direct_kernel(ResizeLaunch L, int blocks_per_plane, int total, int xcd) {
             TOut* o = xrow + (j * 64 + lane) * CC;
 #pragma unroll
             for (int k = 0; k < CC; ++k) {
-                // tap pair (byte k, byte CC + k) -> u16 lanes {lo, hi} (v_perm_b32)
-                const uint32_t sel = (uint32_t)k | (0x0Cu << 8) | ((uint32_t)(CC + k) << 16) | (0x0Cu << 24);
-                const uint32_t top = __builtin_amdgcn_perm(tap[q][0][1], tap[q][0][0], sel);
-                const uint32_t bot = ONE_ROW ? 0u : __builtin_amdgcn_perm(tap[q][NR - 1][1], tap[q][NR - 1][0], sel);
-                const int v = blend_fixed<MODE>(top, bot, wx, wA, wB);
-                if (OUT == kOutSame) o[k] = (TOut)v;
-                else if (OUT == kOutF32) o[k] = (TOut)(float)v;
-                else o[k] = (TOut)normalize_u8v(cn[k], v);
+                const uint32_t top = tap_pair<CC>(tap[q][0][0], tap[q][0][1], k);
+                const uint32_t bot = ONE_ROW ? 0u : tap_pair<CC>(tap[q][NR - 1][0], tap[q][NR - 1][1], k);
+                o[k] = emit_u8<OUT, TOut>(cn[k], blend_fixed<MODE>(top, bot, wx, wA, wB));
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
 
         // ---- LDS -> HBM: dense byte b of the plane's output lives at row
         // b / out_row, column byte b % out_row ---------------------------------
@@ -213,9 +205,7 @@ resize_direct_kernel(ResizeLaunch L, int blocks_per_plane, int total, int xcd) {
                 }
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
     }
 }
 
@@ -356,24 +346,19 @@ resize_cols_kernel(ResizeLaunch L, int col_blocks, int row_groups, int tasks, in
             for (int c = 0; c < CW; ++c) {
 #pragma unroll
                 for (int k = 0; k < CC; ++k) {
-                    // the block's last column (kTail, lane 63) finds its bytes 2 later
+                    // the block's last column (kTail, lane 63) finds its bytes 2 later:
+                    // a per-lane addend to the selector, so tap_pair does not fit
                     const uint32_t sel = ((uint32_t)k | (0x0Cu << 8) | ((uint32_t)(CC + k) << 16) | (0x0Cu << 24)) +
                                          (kTail && c == CW - 1 ? tsh * 0x00010001u : 0u);
                     const uint32_t top = __builtin_amdgcn_perm(tap[r][c][0][1], tap[r][c][0][0], sel);
                     const uint32_t bot =
                         ONE_ROW ? 0u : __builtin_amdgcn_perm(tap[r][c][NR - 1][1], tap[r][c][NR - 1][0], sel);
-                    const int v = blend_fixed<MODE>(top, bot, wx[c], wA, wB);
-                    TOut ov;
-                    if (OUT == kOutSame) ov = (TOut)v;
-                    else if (OUT == kOutF32) ov = (TOut)(float)v;
-                    else ov = (TOut)normalize_u8v(cn[k], v);
-                    xo[(j * 64 * CW + 64 * c + lane) * CC + k] = ov;
+                    xo[(j * 64 * CW + 64 * c + lane) * CC + k] =
+                        emit_u8<OUT, TOut>(cn[k], blend_fixed<MODE>(top, bot, wx[c], wA, wB));
                 }
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
         const int rows = min(kHalf, nrow - g * kHalf);  // uniform
         if (rows > 0) {
             const uint32_t base = (uint32_t)(y0 + g * kHalf) * (uint32_t)L.dst.row_pitch + (uint32_t)(x0 * kOutPx) +
@@ -396,9 +381,7 @@ resize_cols_kernel(ResizeLaunch L, int col_blocks, int row_groups, int tasks, in
                 }
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
     }
 }
 

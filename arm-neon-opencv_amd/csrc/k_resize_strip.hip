@@ -69,25 +69,8 @@ template <int MODE>
 constexpr uint32_t kRowW4 = MODE == VACV_LINEAR_REFERENCE ? 4u : 1u;
 template <int MODE>
 __device__ __forceinline__ uint32_t blend_fixed_hi(uint32_t top, uint32_t bot, us2 wx, uint32_t wA, uint32_t wB) {
-    if constexpr (MODE == VACV_LINEAR_REFERENCE) {
-        const uint32_t ht = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, top), wx, 0u, false);
-        const uint32_t hb = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, bot), wx, 0u, false);
-        return __umul24(ht, wA) + __umul24(hb, wB);
-    } else {
-        return (uint32_t)blend_fixed<MODE>(top, bot, wx, wA, wB) << 24;
-    }
-}
-
-// the channels' values (bits 24..31 of vh[k]) as the pixel's CC bytes
-template <int CC>
-__device__ __forceinline__ uint32_t pack_hi(const uint32_t (&vh)[CC]) {
-    if constexpr (CC == 1) return vh[0] >> 24;
-    else if constexpr (CC == 2) return __builtin_amdgcn_perm(vh[1], vh[0], 0x0C0C0703u);
-    else if constexpr (CC == 3)
-        return __builtin_amdgcn_perm(vh[2], __builtin_amdgcn_perm(vh[1], vh[0], 0x0C0C0703u), 0x0C070100u);
-    else
-        return __builtin_amdgcn_perm(__builtin_amdgcn_perm(vh[3], vh[2], 0x0C0C0703u),
-                                     __builtin_amdgcn_perm(vh[1], vh[0], 0x0C0C0703u), 0x05040100u);
+    if constexpr (MODE == VACV_LINEAR_REFERENCE) return blend_rows(top, bot, wx, wA, wB);
+    else return (uint32_t)blend_fixed<MODE>(top, bot, wx, wA, wB) << 24;
 }
 
 template <int CC, int OUT>
@@ -113,10 +96,7 @@ __device__ __forceinline__ void store_pixel(const uint32_t (&vh)[CC], const Chan
     } else {
         uint32_t f[CC];
 #pragma unroll
-        for (int k = 0; k < CC; ++k) {
-            const int v = (int)(vh[k] >> 24);
-            f[k] = __builtin_bit_cast(uint32_t, OUT == kOutF32 ? (float)v : normalize_u8v(cn[k], v));
-        }
+        for (int k = 0; k < CC; ++k) f[k] = __builtin_bit_cast(uint32_t, emit_u8<OUT, float>(cn[k], (int)(vh[k] >> 24)));
         // the row in voffset here, soffset 0: with a register soffset the
         // compiler leaves out the wait between a store of more than 8 bytes
         // and a VALU write of its data registers, and on gfx950 the next
@@ -145,10 +125,9 @@ resize_strip_kernel(ResizeLaunch L, int strips_x, int groups, int rows_per_group
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform, and said so
-    // XCD-contiguous order: neighbouring strips share the 128-byte lines at
-    // their edges; on one XCD those come from one L2
-    const int per_xcd = (total + 7) / 8;
-    const int id = (int)(blockIdx.x % 8) * per_xcd + (int)(blockIdx.x / 8);
+    // neighbouring strips share the 128-byte lines at their edges; on one XCD
+    // those come from one L2
+    const int id = xcd_block_id(total);
     if (id >= total) return;  // uniform
     const int per_plane = strips_x * groups;
     const int pidx = id / per_plane;
@@ -347,11 +326,8 @@ resize_strip_kernel(ResizeLaunch L, int strips_x, int groups, int rows_per_group
                     const uint32_t wA = wyv[j] & 0xFFFFu, wB = wyv[j] >> 16;
                     uint32_t v[CC];
 #pragma unroll
-                    for (int k = 0; k < CC; ++k) {
-                        const uint32_t sel = (uint32_t)k | (0x0Cu << 8) | ((uint32_t)(CC + k) << 16) | (0x0Cu << 24);
-                        v[k] = blend_fixed_hi<MODE>(__builtin_amdgcn_perm(a1, a0, sel), __builtin_amdgcn_perm(c1, c0, sel),
-                                                    wx, wA, wB);
-                    }
+                    for (int k = 0; k < CC; ++k)
+                        v[k] = blend_fixed_hi<MODE>(tap_pair<CC>(a0, a1, k), tap_pair<CC>(c0, c1, k), wx, wA, wB);
                     // rows past the group (its last batch) repeat the group's last
                     // row (put_rows), value for value: the soffset of a buffer
                     // store is not range-checked, so it always names a real row

@@ -49,12 +49,9 @@ warp_kernel(WarpLaunch L, int gx, int gy, int total) {
     constexpr int kRowBytes = 64 * kPx * CC * (int)sizeof(TOut);  // one wave's output row segment
     __shared__ __attribute__((aligned(16))) unsigned char xch[4][kRowBytes];
 
-    // XCD-aware block order: workgroup b runs on XCD b % 8, and each XCD
-    // walks one contiguous range of (plane, row band, column) blocks, so the
-    // rotated source rows that neighbouring blocks share stay in one L2
-    // (measured: scattered blocks fetched 3.7x the source bytes past L2)
-    const int per_xcd = (total + 7) / 8;
-    const int id = (int)(blockIdx.x % 8) * per_xcd + (int)(blockIdx.x / 8);
+    // each XCD walks one contiguous range of (plane, row band, column) blocks:
+    // the rotated source rows that neighbouring blocks share stay in one L2
+    const int id = xcd_block_id(total);
     if (id >= total) return;  // uniform
     const int pidx = id / (gx * gy);
     const int rem = id - pidx * gx * gy;
@@ -94,9 +91,7 @@ warp_kernel(WarpLaunch L, int gx, int gy, int total) {
         const unsigned char* drow = L.dst.base + (int64_t)img * L.dst.img_pitch + (int64_t)plane * L.dst.plane_pitch +
                                     (int64_t)y * L.dst.row_pitch + (int64_t)xw * CC * sizeof(TOut);
         for (int e = lane; e < vb; e += 64) xch[ry][e] = drow[e];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
     }
 
     // pass q samples the lane block at tile columns cx0 + q*LW (+ lane % LW).
@@ -124,9 +119,7 @@ warp_kernel(WarpLaunch L, int gx, int gy, int total) {
 #pragma unroll
                 for (int k = 0; k < CC; ++k) {
                     if (std::is_same<TIn, uint8_t>::value) {
-                        if (OUT == kOutSame) o[k] = (TOut)vi[k];
-                        else if (OUT == kOutF32) o[k] = (TOut)(float)vi[k];
-                        else o[k] = (TOut)normalize_u8v(cn[k], vi[k]);
+                        o[k] = emit_u8<OUT, TOut>(cn[k], vi[k]);
                     } else {
                         o[k] = (TOut)(OUT == kOutNorm ? normalize_value(vf[k], nmean[k], nstd[k]) : vf[k]);
                     }
@@ -147,9 +140,8 @@ warp_kernel(WarpLaunch L, int gx, int gy, int total) {
         const unsigned char* r0 = sp + (int64_t)sy * rp + (int64_t)sx * CC * sizeof(TIn);
         const unsigned char* r1 = r0 + rp;
         if (std::is_same<TIn, uint8_t>::value) {
-            // SATURATE_CAST_SHORT of a value in (0, 2048]: the +0.5f branch, no clamp
-            const int wy0 = (int)((1.f - ay) * 2048.f + 0.5f), wy1 = 2048 - wy0;
-            const int wx0 = (int)((1.f - ax) * 2048.f + 0.5f), wx1 = 2048 - wx0;
+            const int wy0 = warp_weight(ay), wy1 = 2048 - wy0;
+            const int wx0 = warp_weight(ax), wx1 = 2048 - wx0;
             // the 2*CC tap bytes of each row in ONE dword-aligned buffer load;
             // a load past the plane's end (its last pixel) falls back to bytes
             uint32_t a0 = 0, a1 = 0, c0 = 0, c1 = 0;
@@ -167,28 +159,20 @@ warp_kernel(WarpLaunch L, int gx, int gy, int total) {
                 }
             }
             // warp_affine_naive.cpp:50-54 as (tl*wx0 + tr*wx1)*wy0 + (bl*wx0 +
-            // br*wx1)*wy1: the same int32 value (exact, no overflow: <= 255*2^22),
-            // as one packed u16 dot product per row (v_dot2_u32_u16, tap pair
-            // gathered by v_perm_b32) and two full-rate 24-bit multiplies
-            typedef unsigned short us2 __attribute__((ext_vector_type(2)));
+            // br*wx1)*wy1: the same int32 value (exact, no overflow: <= 255*2^22)
             const us2 wx = __builtin_bit_cast(us2, (uint32_t)wx0 | ((uint32_t)wx1 << 16));
 #pragma unroll
             for (int k = 0; k < CC; ++k) {
                 uint32_t top, bot;
                 if (CC <= 4) {
-                    const uint32_t sel = (uint32_t)k | (0x0Cu << 8) | ((uint32_t)(CC + k) << 16) | (0x0Cu << 24);
-                    top = __builtin_amdgcn_perm(a1, a0, sel);
-                    bot = __builtin_amdgcn_perm(c1, c0, sel);
+                    top = tap_pair<CC>(a0, a1, k);
+                    bot = tap_pair<CC>(c0, c1, k);
                 } else {
                     top = (uint32_t)r0[k] | ((uint32_t)r0[CC + k] << 16);
                     bot = (uint32_t)r1[k] | ((uint32_t)r1[CC + k] << 16);
                 }
-                const uint32_t ht = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, top), wx, 0u, false);
-                const uint32_t hb = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, bot), wx, 0u, false);
-                const int v = (int)((__umul24(ht, (uint32_t)wy0) + __umul24(hb, (uint32_t)wy1)) >> 22);
-                if (OUT == kOutSame) o[k] = (TOut)v;
-                else if (OUT == kOutF32) o[k] = (TOut)(float)v;
-                else o[k] = (TOut)normalize_u8v(cn[k], v);
+                const int v = (int)(blend_rows(top, bot, wx, (uint32_t)wy0, (uint32_t)wy1) >> 22);
+                o[k] = emit_u8<OUT, TOut>(cn[k], v);
             }
         } else {
             const float yy0 = 1.f - ay, yy1 = ay, xa = 1.f - ax, xb = ax;
@@ -215,19 +199,7 @@ warp_kernel(WarpLaunch L, int gx, int gy, int total) {
     unsigned char* drow = const_cast<unsigned char*>(L.dst.base) + (int64_t)img * L.dst.img_pitch +
                           (int64_t)plane * L.dst.plane_pitch + (int64_t)yo * L.dst.row_pitch +
                           (int64_t)xw * CC * sizeof(TOut);
-    const unsigned char* xs = xch[threadIdx.y];
-    if ((reinterpret_cast<uintptr_t>(drow) & 15) == 0) {  // uniform
-        for (int c = lane; c * 16 < vbytes; c += 64) {
-            if (c * 16 + 16 <= vbytes) {
-                __builtin_nontemporal_store(*reinterpret_cast<const u32x4*>(xs + 16 * c),
-                                            reinterpret_cast<u32x4*>(drow) + c);
-            } else {
-                for (int e = c * 16; e < vbytes; ++e) drow[e] = xs[e];
-            }
-        }
-    } else {
-        for (int e = lane; e < vbytes; e += 64) drow[e] = xs[e];
-    }
+    store_row_from_lds(drow, xch[threadIdx.y], vbytes, lane);
 }
 
 // u8 input, BORDER_CONSTANT: the same sampler with its gathers batched.
@@ -246,8 +218,7 @@ warp_u8_kernel(WarpLaunch L, int gx, int gy, int total) {
     constexpr uint32_t kTD = kTapDwords<CC, true>;                // dwords per tap row
     __shared__ __attribute__((aligned(16))) unsigned char xch[4][kRowBytes];
 
-    const int per_xcd = (total + 7) / 8;  // XCD-aware block order (see warp_kernel)
-    const int id = (int)(blockIdx.x % 8) * per_xcd + (int)(blockIdx.x / 8);
+    const int id = xcd_block_id(total);
     if (id >= total) return;  // uniform
     const int pidx = id / (gx * gy);
     const int rem = id - pidx * gx * gy;
@@ -277,7 +248,6 @@ warp_u8_kernel(WarpLaunch L, int gx, int gy, int total) {
     const uint32_t slimit = (uint32_t)L.src.plane_bytes + srs.delta;
     const uint32_t rp32 = (uint32_t)rp;  // plane_bytes < 2^31 (kMaxPlaneBytes)
     TOut* xrow = reinterpret_cast<TOut*>(xch[threadIdx.y]);
-    typedef unsigned short us2v __attribute__((ext_vector_type(2)));
 
 #pragma unroll
     for (int g = 0; g < kPx; g += G) {
@@ -294,9 +264,8 @@ warp_u8_kernel(WarpLaunch L, int gx, int gy, int total) {
             int sx = 0, sy = 0;
             float ax = 0.f, ay = 0.f;
             const bool ok = row_ok && x < L.dst.w && affine_tap(fy, L.src.h, sy, ay) && affine_tap(fx, L.src.w, sx, ax);
-            // SATURATE_CAST_SHORT of a value in (0, 2048]: the +0.5f branch, no clamp
-            const uint32_t w0 = (uint32_t)(int)((1.f - ay) * 2048.f + 0.5f);
-            const uint32_t x0 = (uint32_t)(int)((1.f - ax) * 2048.f + 0.5f);
+            const uint32_t w0 = (uint32_t)warp_weight(ay);
+            const uint32_t x0 = (uint32_t)warp_weight(ax);
             wy0[j] = w0;
             wxp[j] = x0 | ((2048u - x0) << 16);
             const uint32_t o0 = ok ? __umul24((uint32_t)sy, rp32) + (uint32_t)(sx * CC) + srs.delta : srs.delta;
@@ -343,29 +312,18 @@ warp_u8_kernel(WarpLaunch L, int gx, int gy, int total) {
                 a1 = __builtin_amdgcn_alignbyte(tp[j][0][2], tp[j][0][1], sh[j]);
                 c1 = __builtin_amdgcn_alignbyte(tp[j][1][2], tp[j][1][1], sh1[j]);
             }
-            const us2v wx = __builtin_bit_cast(us2v, wxp[j]);
+            const us2 wx = __builtin_bit_cast(us2, wxp[j]);
             const uint32_t wA = wy0[j], wB = 2048u - wy0[j];
 #pragma unroll
             for (int k = 0; k < CC; ++k) {
                 // warp_affine_naive.cpp:50-54 as (tl*wx0 + tr*wx1)*wy0 +
                 // (bl*wx0 + br*wx1)*wy1 (exact int32, <= 255*2^22)
-                const uint32_t sel = (uint32_t)k | (0x0Cu << 8) | ((uint32_t)(CC + k) << 16) | (0x0Cu << 24);
-                const uint32_t top = __builtin_amdgcn_perm(a1, a0, sel);
-                const uint32_t bot = __builtin_amdgcn_perm(c1, c0, sel);
-                const uint32_t ht = __builtin_amdgcn_udot2(__builtin_bit_cast(us2v, top), wx, 0u, false);
-                const uint32_t hb = __builtin_amdgcn_udot2(__builtin_bit_cast(us2v, bot), wx, 0u, false);
-                const int v = (int)((__umul24(ht, wA) + __umul24(hb, wB)) >> 22);
-                TOut ov;
-                if (OUT == kOutSame) ov = (TOut)v;
-                else if (OUT == kOutF32) ov = (TOut)(float)v;
-                else ov = (TOut)normalize_u8v(cn[k], v);
-                o[k] = val[j] ? ov : bval[k];
+                const int v = (int)(blend_rows(tap_pair<CC>(a0, a1, k), tap_pair<CC>(c0, c1, k), wx, wA, wB) >> 22);
+                o[k] = val[j] ? emit_u8<OUT, TOut>(cn[k], v) : bval[k];
             }
         }
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
 
     // ---- the wave's row, LDS -> HBM in 16-byte chunks ---------------------
     if (!row_ok) return;
@@ -373,19 +331,7 @@ warp_u8_kernel(WarpLaunch L, int gx, int gy, int total) {
     unsigned char* drow = const_cast<unsigned char*>(L.dst.base) + (int64_t)img * L.dst.img_pitch +
                           (int64_t)plane * L.dst.plane_pitch + (int64_t)y * L.dst.row_pitch +
                           (int64_t)xw * CC * sizeof(TOut);
-    const unsigned char* xs = xch[threadIdx.y];
-    if ((reinterpret_cast<uintptr_t>(drow) & 15) == 0) {  // uniform
-        for (int c = lane; c * 16 < vbytes; c += 64) {
-            if (c * 16 + 16 <= vbytes) {
-                __builtin_nontemporal_store(*reinterpret_cast<const u32x4*>(xs + 16 * c),
-                                            reinterpret_cast<u32x4*>(drow) + c);
-            } else {
-                for (int e = c * 16; e < vbytes; ++e) drow[e] = xs[e];
-            }
-        }
-    } else {
-        for (int e = lane; e < vbytes; e += 64) drow[e] = xs[e];
-    }
+    store_row_from_lds(drow, xch[threadIdx.y], vbytes, lane);
 }
 
 // default: 8 or 10 lane blocks per wave for byte output, whichever pads the

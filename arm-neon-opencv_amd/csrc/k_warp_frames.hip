@@ -123,8 +123,7 @@ warp_ring_kernel(WarpLaunch L, int gx, int gy, int kf, int S, int rows_max, int 
     const int tiles = gx * gy;
     const int nfr = L.n * L.src.planes;
     const int total = tiles * ((nfr + kf - 1) / kf);
-    const int per_xcd = (total + 7) / 8;
-    const int id = (int)(blockIdx.x % 8) * per_xcd + (int)(blockIdx.x / 8);
+    const int id = xcd_block_id(total);
     if (id >= total) return;  // uniform
     const int fg = id / tiles, tile = id - fg * tiles;
     const int by = tile / gx, bx = tile - by * gx;
@@ -156,6 +155,7 @@ warp_ring_kernel(WarpLaunch L, int gx, int gy, int kf, int S, int rows_max, int 
         const bool ok = (x < L.dst.w) & (y < L.dst.h) & (fx >= 0.f) & (fx < wlim) & (fy >= 0.f) & (fy < hlim);
         const int sx = ok ? (int)fx : 0, sy = ok ? (int)fy : 0;
         const float ax = fx - (float)sx, ay = fy - (float)sy;
+        // written out, not warp_weight: the call reschedules every instance of this kernel
         const uint32_t w0 = (uint32_t)(int)((1.f - ay) * 2048.f + 0.5f);
         const uint32_t v0 = (uint32_t)(int)((1.f - ax) * 2048.f + 0.5f);
         sxy[j] = (uint32_t)sx | ((uint32_t)sy << 16);
@@ -349,16 +349,15 @@ warp_ring_kernel(WarpLaunch L, int gx, int gy, int kf, int S, int rows_max, int 
         uint32_t vv[CC];
 #pragma unroll
         for (int k = 0; k < CC; ++k) {
-            // channel k of the left tap (byte k) and of the right tap (byte CC + k)
-            const uint32_t sel = (uint32_t)k | (0x0Cu << 8) | ((uint32_t)(CC + k) << 16) | (0x0Cu << 24);
-            const uint32_t top = __builtin_amdgcn_perm(thi, tlo, sel);
-            const uint32_t bot = __builtin_amdgcn_perm(bhi, blo, sel);
+            // written out, not blend_rows: the call reschedules every instance of this kernel
+            const uint32_t top = tap_pair<CC>(tlo, thi, k), bot = tap_pair<CC>(blo, bhi, k);
             const uint32_t ht = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, top), wx, 0u, false);
             const uint32_t hb = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, bot), wx, 0u, false);
             vv[k] = __umul24(ht, wA) + __umul24(hb, wB);  // warp_affine_naive.cpp:50-54, x4
         }
         const uint32_t drow = (uint32_t)y * dpitch + drs.delta;
         if constexpr (OUT == kOutSame) {
+            // written out, not pack_hi: the call took CC = 2 past 64 VGPRs (an occupancy step)
             uint32_t own;
             if constexpr (CC == 1) {
                 own = vv[0] >> 24;
@@ -376,9 +375,7 @@ warp_ring_kernel(WarpLaunch L, int gx, int gy, int kf, int S, int rows_max, int 
                 unsigned char* xw = xch + (j & 1) * kRowB;
                 if ((lane & 3) < CC) *reinterpret_cast<uint32_t*>(xw + 4 * ((lane >> 2) * CC + (lane & 3))) = word;
                 if (j & 1) {
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                    wave_lds_sync();
                     constexpr int kChunks = kRowB / 16;
                     const int m = lane % (2 * kChunks);
                     const u32x4 v = *reinterpret_cast<const u32x4*>(xch + 16 * m);
@@ -632,8 +629,7 @@ warp_exp_kernel(WarpLaunch L, int gx, int gy, int kf, int slot_bytes, int exp_un
     const int tiles = gx * gy;
     const int nfr = L.n;
     const int total = tiles * ((nfr + kf - 1) / kf);
-    const int per_xcd = (total + 7) / 8;
-    const int id = (int)(blockIdx.x % 8) * per_xcd + (int)(blockIdx.x / 8);
+    const int id = xcd_block_id(total);
     if (id >= total) return;  // uniform
     const int fg = id / tiles, tile = id - fg * tiles;
     const int by = tile / gx, bx = tile - by * gx;
@@ -675,6 +671,7 @@ warp_exp_kernel(WarpLaunch L, int gx, int gy, int kf, int slot_bytes, int exp_un
             sx = ok ? (int)fx : 0;
             sy = ok ? (int)fy : 0;
             const float ax = fx - (float)sx, ay = fy - (float)sy;
+            // written out, not warp_weight: the call took this kernel's spills from 6 to 18
             const uint32_t w0 = (uint32_t)(int)((1.f - ay) * 2048.f + 0.5f);
             const uint32_t v0 = (uint32_t)(int)((1.f - ax) * 2048.f + 0.5f);
             vwa[j] = ok ? (v0 | ((4u * w0) << 16)) : (2048u | (8192u << 16));
@@ -934,14 +931,8 @@ warp_exp_kernel(WarpLaunch L, int gx, int gy, int kf, int slot_bytes, int exp_un
         const us2 wx = __builtin_bit_cast(us2, wxp[j]);
         const uint32_t wA = wa[j], wB = 8192u - wa[j];
 #pragma unroll
-        for (int k = 0; k < CC; ++k) {
-            const uint32_t sel = (uint32_t)k | (0x0Cu << 8) | ((uint32_t)(4 + k) << 16) | (0x0Cu << 24);
-            const uint32_t top = __builtin_amdgcn_perm(tr, tl, sel);
-            const uint32_t bot = __builtin_amdgcn_perm(br, bl, sel);
-            const uint32_t ht = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, top), wx, 0u, false);
-            const uint32_t hb = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, bot), wx, 0u, false);
-            vv[k] = __umul24(ht, wA) + __umul24(hb, wB);
-        }
+        for (int k = 0; k < CC; ++k)  // the taps are 4-byte pixels here
+            vv[k] = blend_rows(tap_pair<4>(tl, tr, k), tap_pair<4>(bl, br, k), wx, wA, wB);
     };
     ChanNorm cn[CC];
     auto emit = [&](auto full_c, int f, int j, const uint32_t (&vv)[CC]) {
@@ -951,13 +942,11 @@ warp_exp_kernel(WarpLaunch L, int gx, int gy, int kf, int slot_bytes, int exp_un
         unsigned char* dbase = const_cast<unsigned char*>(L.dst.base) + (int64_t)f * L.dst.img_pitch;
         const Rsrc drs = make_rsrc(dbase, L.dst.plane_bytes);
         if constexpr (OUT == kOutSame) {
-            const uint32_t own = __builtin_amdgcn_perm(vv[2], __builtin_amdgcn_perm(vv[1], vv[0], 0x0C0C0703u), 0x0C070100u);
+            const uint32_t own = pack_hi<CC>(vv);
             if constexpr (FULL) {
                 *reinterpret_cast<uint32_t*>(xch + 256 * (j & 3) + 4 * lane) = own;
                 if ((j & 3) == 3) {
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                    wave_lds_sync();
                     // 4 rows of 64 pixels; a lane stores 4 pixels, 12 bytes
                     const int r = lane >> 4, q = lane & 15;
                     const u32x4 p = *reinterpret_cast<const u32x4*>(xch + 256 * r + 16 * q);
@@ -986,9 +975,7 @@ warp_exp_kernel(WarpLaunch L, int gx, int gy, int kf, int slot_bytes, int exp_un
             if constexpr (FULL) {
 #pragma unroll
                 for (int k = 0; k < CC; ++k) *reinterpret_cast<uint32_t*>(xch + 12 * lane + 4 * k) = o[k];
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                wave_lds_sync();
                 const u32x4 p = *reinterpret_cast<const u32x4*>(xch + 16 * (lane % (3 * 16)));
                 const uint32_t off = lane < 3 * 16 ? (uint32_t)y * dpitch + drs.delta +
                                                          (uint32_t)((x - lane) * CC * 4 + 16 * lane)

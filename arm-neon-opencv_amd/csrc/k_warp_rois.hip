@@ -105,11 +105,9 @@ warp_rois_kernel(WarpRoisLaunch L, int tiles, int total) {
     __shared__ float s_inv[6];
     __shared__ int s_frame;
 
-    // XCD-aware block order (see warp_kernel): an XCD walks a contiguous
-    // range of (ROI, tile), so the tiles of one ROI, which share source lines,
-    // meet in one L2
-    const int per_xcd = (total + 7) / 8;
-    const int id = (int)(blockIdx.x % 8) * per_xcd + (int)(blockIdx.x / 8);
+    // an XCD walks a contiguous range of (ROI, tile), so the tiles of one ROI,
+    // which share source lines, meet in one L2
+    const int id = xcd_block_id(total);
     if (id >= total) return;  // uniform
     const int roi = id / tiles;
     const int tile = id - roi * tiles;
@@ -209,8 +207,7 @@ warp_rois_kernel(WarpRoisLaunch L, int tiles, int total) {
 #pragma unroll
                 for (int k = 0; k < CC; ++k) {
                     if (kU8) {
-                        if (OUT == kOutSame) *o[k] = (TOut)vi[k];
-                        else *o[k] = (TOut)normalize_u8v(cn[k], vi[k]);
+                        *o[k] = emit_u8<OUT, TOut>(cn[k], vi[k]);
                     } else {
                         *o[k] = (TOut)(OUT == kOutNorm ? normalize_value(vf[k], nmean[k], nstd[k]) : vf[k]);
                     }
@@ -225,9 +222,8 @@ warp_rois_kernel(WarpRoisLaunch L, int tiles, int total) {
                             (uint32_t)(sx * CC * (int)sizeof(TIn)) + srs.delta;
         const uint32_t o1 = o0 + rp32;
         if constexpr (kU8) {
-            // SATURATE_CAST_SHORT of a value in (0, 2048]: the +0.5f branch, no clamp
-            const int wy0 = (int)((1.f - ay) * 2048.f + 0.5f), wy1 = 2048 - wy0;
-            const int wx0 = (int)((1.f - ax) * 2048.f + 0.5f), wx1 = 2048 - wx0;
+            const int wy0 = warp_weight(ay), wy1 = 2048 - wy0;
+            const int wx0 = warp_weight(ax), wx1 = 2048 - wx0;
             // the 2*CC tap bytes of each row in ONE dword-aligned buffer load;
             // a load past the frame's end (its last pixel) falls back to bytes
             uint32_t a0 = 0, a1 = 0, c0 = 0, c1 = 0;
@@ -248,14 +244,12 @@ warp_rois_kernel(WarpRoisLaunch L, int tiles, int total) {
             const us2 wx = __builtin_bit_cast(us2, (uint32_t)wx0 | ((uint32_t)wx1 << 16));
 #pragma unroll
             for (int k = 0; k < CC; ++k) {
-                const uint32_t sel = (uint32_t)k | (0x0Cu << 8) | ((uint32_t)(CC + k) << 16) | (0x0Cu << 24);
-                const uint32_t top = __builtin_amdgcn_perm(a1, a0, sel);
-                const uint32_t bot = __builtin_amdgcn_perm(c1, c0, sel);
+                // written out, not blend_rows: with the call the 1080p u8 crops measured 1.5-3 % slower
+                const uint32_t top = tap_pair<CC>(a0, a1, k), bot = tap_pair<CC>(c0, c1, k);
                 const uint32_t ht = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, top), wx, 0u, false);
                 const uint32_t hb = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, bot), wx, 0u, false);
                 const int v = (int)((__umul24(ht, (uint32_t)wy0) + __umul24(hb, (uint32_t)wy1)) >> 22);
-                if (OUT == kOutSame) *o[k] = (TOut)v;
-                else *o[k] = (TOut)normalize_u8v(cn[k], v);
+                *o[k] = emit_u8<OUT, TOut>(cn[k], v);
             }
         } else {
             const float yy0 = 1.f - ay, yy1 = ay, xa = 1.f - ax, xb = ax;

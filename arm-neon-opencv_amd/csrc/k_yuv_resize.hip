@@ -249,17 +249,10 @@ yuv_resize_kernel(YuvResizeLaunch L) {
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
                 const uint32_t top = pa[k], bot = pb[k];
-                const int v = blend_fixed<MODE>(top, bot, wx, wA, wB);
-                TOut ov;
-                if (OUT == kOutSame) ov = (TOut)v;
-                else if (OUT == kOutF32) ov = (TOut)(float)v;
-                else ov = (TOut)normalize_u8v(cn[k], v);
-                xo[CHW ? k * kGroupPx + q : q * 3 + k] = ov;
+                xo[CHW ? k * kGroupPx + q : q * 3 + k] = emit_u8<OUT, TOut>(cn[k], blend_fixed<MODE>(top, bot, wx, wA, wB));
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
 
         // ---- LDS -> HBM: dense byte b of a plane's output lives at row
         // b / out_row, column byte b % out_row --------------------------------
@@ -273,33 +266,10 @@ yuv_resize_kernel(YuvResizeLaunch L) {
                 const unsigned char* xs = xch[threadIdx.y] + k * kSpan;
                 const bool chunked = (reinterpret_cast<uintptr_t>(dp) & 15) == 0 && (L.dst_row & 15) == 0 &&
                                      (dense || (out_row & 15) == 0);  // 16-byte chunks never straddle rows
-                if (chunked) {
-                    for (uint32_t c = lane; c * 16 < vbytes; c += 64) {
-                        const uint32_t b = b0 + 16 * c;
-                        uint32_t off = b;
-                        if (!dense) {
-                            const uint32_t r = b / out_row;
-                            off = r * rowp + (b - r * out_row);
-                        }
-                        if (c * 16 + 16 <= vbytes) {
-                            __builtin_nontemporal_store(*reinterpret_cast<const u32x4*>(xs + 16 * c),
-                                                        reinterpret_cast<u32x4*>(dp + off));
-                        } else {
-                            for (uint32_t e = c * 16; e < vbytes; ++e) dp[off + (e - c * 16)] = xs[e];
-                        }
-                    }
-                } else {
-                    for (uint32_t e = lane; e < vbytes; e += 64) {
-                        const uint32_t b = b0 + e;
-                        const uint32_t r = b / out_row;
-                        dp[(int64_t)r * rowp + (b - r * out_row)] = xs[e];
-                    }
-                }
+                store_range_from_lds(dp, xs, b0, vbytes, out_row, rowp, dense, chunked, lane);
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
     }
 }
 
@@ -465,12 +435,8 @@ yuv_cols_kernel(YuvResizeLaunch L, int col_blocks, int row_groups) {
 #pragma unroll
                     for (int k = 0; k < 3; ++k) {
                         const int v = (int)((q[k] >> (16 * e)) & 0xFFu);
-                        TOut ov;
-                        if (OUT == kOutSame) ov = (TOut)v;
-                        else if (OUT == kOutF32) ov = (TOut)(float)v;
-                        else ov = (TOut)normalize_u8v(cn[k], v);
                         const int px = jj * 64 * CW + 64 * cc + lane;
-                        xo[CHW ? k * (HALF * 64 * CW) + px : px * 3 + k] = ov;
+                        xo[CHW ? k * (HALF * 64 * CW) + px : px * 3 + k] = emit_u8<OUT, TOut>(cn[k], v);
                     }
                 }
                 continue;
@@ -490,18 +456,12 @@ yuv_cols_kernel(YuvResizeLaunch L, int col_blocks, int row_groups) {
 #pragma unroll
                 for (int k = 0; k < 3; ++k) {
                     const int v = blend_fixed<MODE>(pa[k], pb[k], wx[c], wA, wB);
-                    TOut ov;
-                    if (OUT == kOutSame) ov = (TOut)v;
-                    else if (OUT == kOutF32) ov = (TOut)(float)v;
-                    else ov = (TOut)normalize_u8v(cn[k], v);
                     const int px = j * 64 * CW + 64 * c + lane;  // pixel in the round
-                    xo[CHW ? k * (HALF * 64 * CW) + px : px * 3 + k] = ov;
+                    xo[CHW ? k * (HALF * 64 * CW) + px : px * 3 + k] = emit_u8<OUT, TOut>(cn[k], v);
                 }
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
         const int rows = min(HALF, nrow - g * HALF);  // uniform
         if (rows > 0) {
             const uint32_t base = (uint32_t)(y0 + g * HALF) * (uint32_t)L.dst_row +
@@ -529,9 +489,7 @@ yuv_cols_kernel(YuvResizeLaunch L, int col_blocks, int row_groups) {
                 }
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
     }
 }
 

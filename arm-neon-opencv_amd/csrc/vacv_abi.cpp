@@ -72,6 +72,12 @@ int load(const vacv_image* d, Img& m) {
     return VACV_OK;
 }
 
+// a source and its destination: the source's status first
+int load2(const vacv_image* src_d, const vacv_image* dst_d, Img& src, Img& dst) {
+    const int st = load(src_d, src);
+    return st ? st : load(dst_d, dst);
+}
+
 bool dense(const Img& m) {
     const int64_t row = (int64_t)m.w * (m.layout == VACV_NHWC ? m.c : 1) * m.es;
     if (m.row != row) return false;
@@ -250,12 +256,19 @@ struct FusedSums {
     int64_t* acc;                // [n][cc][2], zero between calls (the column kernel's fixed-point sums)
 };
 
+// The launch's output kind for the requested one (fp32 from an fp32 source is
+// the source's own type) and whether dst's dtype is the one it produces.
+int resolve_out(const Img& src, const Img& dst, int out_kind, int& out) {
+    out = (src.dtype == VACV_FP32 && out_kind == kOutF32) ? kOutSame : out_kind;
+    const int want = out == kOutSame ? src.dtype : VACV_FP32;
+    return dst.dtype == want ? VACV_OK : VACV_ERR_INVALID_ARG;
+}
+
 int resize_impl(const vacv_image* src_d, const vacv_image* dst_d, int interpolation, int mode, int out_kind,
                 const NormSpec* ns, hipStream_t s, double fx = 0.0, double fy = 0.0, FusedSums* fs = nullptr) {
     Img src, dst;
-    int st = load(src_d, src);
+    int st = load2(src_d, dst_d, src, dst);
     if (st) return st;
-    if ((st = load(dst_d, dst))) return st;
     if (src.n != dst.n || src.c != dst.c || src.layout != dst.layout) return VACV_ERR_INVALID_ARG;
     if (src.layout == VACV_NHWC && src.c > 4) return VACV_ERR_UNSUPPORTED;
     if (mode < VACV_LINEAR_REFERENCE || mode > VACV_LINEAR_OPENCV) return VACV_ERR_INVALID_ARG;
@@ -293,10 +306,7 @@ int resize_impl(const vacv_image* src_d, const vacv_image* dst_d, int interpolat
         // resize.cpp:44-49 hands it to cv::resize (recursing forever without
         // OpenCV); OpenCV 2.4's resizeNN semantics
         if (src.dtype != VACV_INT8 && src.dtype != VACV_FP32) return VACV_ERR_UNSUPPORTED;
-        L.out = out_kind;
-        if (src.dtype == VACV_FP32 && L.out == kOutF32) L.out = kOutSame;
-        const int want = L.out == kOutSame ? src.dtype : VACV_FP32;
-        if (dst.dtype != want) return VACV_ERR_INVALID_ARG;
+        if ((st = resolve_out(src, dst, out_kind, L.out))) return st;
         L.scale_xd = 1. / (fx > 0 ? fx : (double)dst.w / src.w);  // ifx, as cv::resize computes it
         L.scale_yd = 1. / (fy > 0 ? fy : (double)dst.h / src.h);
         return hip_status(launch_resize_nearest(L, s));
@@ -306,10 +316,7 @@ int resize_impl(const vacv_image* src_d, const vacv_image* dst_d, int interpolat
         // DBL_EPSILON, resizeArea_'s weight tables for other down-scales and
         // its bilinear resize with area-mode taps for up-scales (k_area.hip)
         if (src.dtype != VACV_INT8 && src.dtype != VACV_FP32) return VACV_ERR_UNSUPPORTED;
-        L.out = out_kind;
-        if (src.dtype == VACV_FP32 && L.out == kOutF32) L.out = kOutSame;
-        const int want = L.out == kOutSame ? src.dtype : VACV_FP32;
-        if (dst.dtype != want) return VACV_ERR_INVALID_ARG;
+        if ((st = resolve_out(src, dst, out_kind, L.out))) return st;
         const double ifx = fx > 0 ? fx : (double)dst.w / src.w, ify = fy > 0 ? fy : (double)dst.h / src.h;
         const double sx = 1. / ifx, sy = 1. / ify;
         const double ix = std::nearbyint(sx), iy = std::nearbyint(sy);
@@ -331,10 +338,7 @@ int resize_impl(const vacv_image* src_d, const vacv_image* dst_d, int interpolat
         // resize.cpp:46-48 hands it to cv::resize; OpenCV 2.4's 8x8 Lanczos
         // (k_lanczos.hip), u8 in fixed point, fp32 in float
         if (src.dtype != VACV_INT8 && src.dtype != VACV_FP32) return VACV_ERR_UNSUPPORTED;
-        L.out = out_kind;
-        if (src.dtype == VACV_FP32 && L.out == kOutF32) L.out = kOutSame;
-        const int want = L.out == kOutSame ? src.dtype : VACV_FP32;
-        if (dst.dtype != want) return VACV_ERR_INVALID_ARG;
+        if ((st = resolve_out(src, dst, out_kind, L.out))) return st;
         const double ifx = fx > 0 ? fx : (double)dst.w / src.w, ify = fy > 0 ? fy : (double)dst.h / src.h;
         return launch_resize_lanczos(L, ifx, ify, s);
     } else {
@@ -393,6 +397,12 @@ int copy_rows(const Img& src, const Img& dst, int64_t src_off, int rows_h, int64
     return hip_status(launch_row_copy(L, s));
 }
 
+// every row of src to dst
+int clone_rows(const Img& src, const Img& dst, hipStream_t s) {
+    const int cc = src.layout == VACV_NHWC ? src.c : 1;
+    return copy_rows(src, dst, 0, src.h, (int64_t)src.w * cc * src.es, s);
+}
+
 int dtype_convert(const Img& src, const Img& dst, hipStream_t s) {
     if (!dense(src) || !dense(dst)) return VACV_ERR_UNSUPPORTED;
     DtypeLaunch L{};
@@ -419,9 +429,8 @@ int border_values(const Img& src, const double* bv, float out[4]) {
 int warp_impl(const vacv_image* src_d, const vacv_image* dst_d, const float m[6], int flags, int border_mode,
               const double bv[4], int out_kind, const NormSpec* ns, hipStream_t s) {
     Img src, dst;
-    int st = load(src_d, src);
+    int st = load2(src_d, dst_d, src, dst);
     if (st) return st;
-    if ((st = load(dst_d, dst))) return st;
     if (!m) return VACV_ERR_INVALID_ARG;
     if (src.n != dst.n || src.c != dst.c || src.layout != dst.layout) return VACV_ERR_INVALID_ARG;
     if (src.dtype != VACV_INT8 && src.dtype != VACV_FP32) return VACV_ERR_UNSUPPORTED;
@@ -443,10 +452,7 @@ int warp_impl(const vacv_image* src_d, const vacv_image* dst_d, const float m[6]
     L.src = geom(src);
     L.dst = geom(dst);
     L.n = src.n;
-    L.out = out_kind;
-    if (src.dtype == VACV_FP32 && out_kind == kOutF32) L.out = kOutSame;
-    const int want = (L.out == kOutSame) ? src.dtype : VACV_FP32;
-    if (dst.dtype != want) return VACV_ERR_INVALID_ARG;
+    if ((st = resolve_out(src, dst, out_kind, L.out))) return st;
     if (inverse_map) std::memcpy(L.inv, m, sizeof(L.inv));
     else vacv_invert_affine(m, L.inv);
     border_values(src, bv, L.border);
@@ -483,9 +489,8 @@ int warp_impl(const vacv_image* src_d, const vacv_image* dst_d, const float m[6]
 int warp_rois_impl(const vacv_image* src_d, const vacv_image* dst_d, const float* m, const int32_t* src_index,
                    int flags, int border_mode, const double bv[4], const NormSpec* ns, hipStream_t s) {
     Img src, dst;
-    int st = load(src_d, src);
+    int st = load2(src_d, dst_d, src, dst);
     if (st) return st;
-    if ((st = load(dst_d, dst))) return st;
     if (!m) return VACV_ERR_INVALID_ARG;
     if (src.c != dst.c) return VACV_ERR_INVALID_ARG;
     if (!src_index && src.n != 1 && src.n != dst.n) return VACV_ERR_INVALID_ARG;
@@ -531,9 +536,8 @@ int color_code(int code, int& v_first, int& rgb) {
 int color_impl(const vacv_image* src_d, const vacv_image* dst_d, int code, int out_kind, const NormSpec* ns,
                hipStream_t s) {
     Img src, dst;
-    int st = load(src_d, src);
+    int st = load2(src_d, dst_d, src, dst);
     if (st) return st;
-    if ((st = load(dst_d, dst))) return st;
     int v_first, rgb;
     if ((st = color_code(code, v_first, rgb))) return st;
     if (src.dtype != VACV_INT8 || src.c != 1) return VACV_ERR_INVALID_ARG;
@@ -564,9 +568,8 @@ int color_impl(const vacv_image* src_d, const vacv_image* dst_d, int code, int o
 // 139-141), OpenCV 2.4's arithmetic (k_color_cv.hip).
 int color_cv_impl(const vacv_image* src_d, const vacv_image* dst_d, int code, hipStream_t s) {
     Img src, dst;
-    int st = load(src_d, src);
+    int st = load2(src_d, dst_d, src, dst);
     if (st) return st;
-    if ((st = load(dst_d, dst))) return st;
     if (src.layout != VACV_NHWC || dst.layout != VACV_NHWC || src.c != 1 || dst.n != src.n) return VACV_ERR_INVALID_ARG;
     CvColorLaunch L{};
     L.src = src.data;
@@ -613,9 +616,8 @@ int color_cv_impl(const vacv_image* src_d, const vacv_image* dst_d, int code, hi
 int yuv_resize_impl(const vacv_image* src_d, const vacv_image* dst_d, int code, int interpolation, int mode,
                     int out_kind, const NormSpec* ns, hipStream_t s) {
     Img src, dst;
-    int st = load(src_d, src);
+    int st = load2(src_d, dst_d, src, dst);
     if (st) return st;
-    if ((st = load(dst_d, dst))) return st;
     int v_first, rgb;
     if ((st = color_code(code, v_first, rgb))) return st;
     if (interpolation != VACV_INTER_LINEAR) return VACV_ERR_UNSUPPORTED;
@@ -748,9 +750,8 @@ int64_t vacv_image_bytes(const vacv_image* d) {
 
 int vacv_crop(const vacv_image* src_d, const vacv_image* dst_d, int left, int top, void* stream) {
     Img src, dst;
-    int st = load(src_d, src);
+    int st = load2(src_d, dst_d, src, dst);
     if (st) return st;
-    if ((st = load(dst_d, dst))) return st;
     if (src.n != dst.n || src.c != dst.c || src.layout != dst.layout || src.dtype != dst.dtype)
         return VACV_ERR_INVALID_ARG;
     if (left < 0 || top < 0 || left + dst.w > src.w || top + dst.h > src.h) return VACV_ERR_INVALID_ARG;
@@ -761,9 +762,8 @@ int vacv_crop(const vacv_image* src_d, const vacv_image* dst_d, int left, int to
 
 int vacv_change_layout(const vacv_image* src_d, const vacv_image* dst_d, void* stream) {
     Img src, dst;
-    int st = load(src_d, src);
+    int st = load2(src_d, dst_d, src, dst);
     if (st) return st;
-    if ((st = load(dst_d, dst))) return st;
     if (src.n != dst.n || src.w != dst.w || src.h != dst.h || src.c != dst.c || src.dtype != dst.dtype)
         return VACV_ERR_INVALID_ARG;
     hipStream_t s = (hipStream_t)stream;
@@ -773,10 +773,9 @@ int vacv_change_layout(const vacv_image* src_d, const vacv_image* dst_d, void* s
             if (!dense(src) || !dense(dst)) return VACV_ERR_UNSUPPORTED;
             Img a = src, b = dst;
             a.layout = b.layout = VACV_NHWC;
-            return copy_rows(a, b, 0, a.h, (int64_t)a.w * a.es, s);
+            return clone_rows(a, b, s);
         }
-        const int cc = src.layout == VACV_NHWC ? src.c : 1;
-        return copy_rows(src, dst, 0, src.h, (int64_t)src.w * cc * src.es, s);
+        return clone_rows(src, dst, s);
     }
     if (!dense(src) || !dense(dst)) return VACV_ERR_UNSUPPORTED;
     LayoutLaunch L{};
@@ -795,15 +794,11 @@ int vacv_change_layout(const vacv_image* src_d, const vacv_image* dst_d, void* s
 
 int vacv_change_dtype(const vacv_image* src_d, const vacv_image* dst_d, void* stream) {
     Img src, dst;
-    int st = load(src_d, src);
+    int st = load2(src_d, dst_d, src, dst);
     if (st) return st;
-    if ((st = load(dst_d, dst))) return st;
     if (!same_shape(src, dst)) return VACV_ERR_INVALID_ARG;
     hipStream_t s = (hipStream_t)stream;
-    if (src.dtype == dst.dtype) {
-        const int cc = src.layout == VACV_NHWC ? src.c : 1;
-        return copy_rows(src, dst, 0, src.h, (int64_t)src.w * cc * src.es, s);
-    }
+    if (src.dtype == dst.dtype) return clone_rows(src, dst, s);
     const bool ok = (src.dtype == VACV_INT8 && dst.dtype == VACV_FP32) ||
                     (src.dtype == VACV_FP32 && dst.dtype == VACV_INT8);
     if (!ok) return VACV_ERR_UNSUPPORTED;  // tensor.cpp:494-499 returns garbage
@@ -812,19 +807,15 @@ int vacv_change_dtype(const vacv_image* src_d, const vacv_image* dst_d, void* st
 
 int vacv_resize(const vacv_image* src_d, const vacv_image* dst_d, int interpolation, int mode, void* stream) {
     Img src, dst;
-    int st = load(src_d, src);
+    int st = load2(src_d, dst_d, src, dst);
     if (st) return st;
-    if ((st = load(dst_d, dst))) return st;
     hipStream_t s = (hipStream_t)stream;
     if (src.w == dst.w && src.h == dst.h && (interpolation == VACV_INTER_LINEAR || interpolation == VACV_INTER_CUBIC) &&
         same_shape(src, dst)) {
         // resize.cpp:58-61 short-circuits equal sizes with a copy (the
         // reference copies w*h*c BYTES, a quarter of an fp32 image; this
         // copies the whole image)
-        if (src.dtype == dst.dtype) {
-            const int cc = src.layout == VACV_NHWC ? src.c : 1;
-            return copy_rows(src, dst, 0, src.h, (int64_t)src.w * cc * src.es, s);
-        }
+        if (src.dtype == dst.dtype) return clone_rows(src, dst, s);
         if (src.dtype == VACV_INT8 && dst.dtype == VACV_FP32 && interpolation == VACV_INTER_CUBIC) {
             if (dense(src) && dense(dst)) return dtype_convert(src, dst, s);
             // a pitched source or destination (accepted at every other output
@@ -921,9 +912,8 @@ int vacv_cvt_color(const vacv_image* src, const vacv_image* dst, int code, void*
 int vacv_normalize(const vacv_image* src_d, const vacv_image* dst_d, const float* mean, const float* stddev,
                    void* stream) {
     Img src, dst;
-    int st = load(src_d, src);
+    int st = load2(src_d, dst_d, src, dst);
     if (st) return st;
-    if ((st = load(dst_d, dst))) return st;
     if (!same_shape(src, dst) || dst.dtype != VACV_FP32) return VACV_ERR_INVALID_ARG;
     if (src.dtype != VACV_INT8 && src.dtype != VACV_FP32) return VACV_ERR_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
@@ -969,9 +959,8 @@ int resize_sums(const vacv_image* src_d, const vacv_image* dst_d, int interpolat
     if (!sums) return VACV_ERR_INVALID_ARG;
     hipStream_t s = (hipStream_t)stream;
     Img src, dst;
-    int st = load(src_d, src);
+    int st = load2(src_d, dst_d, src, dst);
     if (st) return st;
-    if ((st = load(dst_d, dst))) return st;
     if (interpolation == VACV_INTER_CUBIC && src.dtype == VACV_INT8 && dst.dtype == VACV_FP32 &&
         dst.layout == VACV_NHWC && dst.c <= 3 && dense(dst) && src.n == dst.n) {
         const int64_t groups = cubic_sums_groups_bound(dst.w, dst.h);  // the workspace's bound

@@ -12,6 +12,25 @@
 namespace vacv {
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned short us2 __attribute__((ext_vector_type(2)));
+
+// XCD-contiguous block order of a grid padded to a multiple of 8 blocks:
+// workgroup b runs on XCD b % 8, so the id that block b works on is laid out
+// so that each XCD walks one contiguous range of [0, total).  Blocks that
+// share source lines then meet in one L2 (warp: scattered blocks fetched 3.7x
+// the source bytes past L2).  The caller returns when the id is >= total.
+__device__ __forceinline__ int xcd_block_id(int total) {
+    const int per_xcd = (total + 7) / 8;
+    return (int)(blockIdx.x % 8) * per_xcd + (int)(blockIdx.x / 8);
+}
+
+// Lanes of a wave hand bytes to each other through LDS: order the writes
+// before the reads without a workgroup barrier.
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
 
 // Cache-policy aux bits of the streaming buffer loads / stores (gfx950:
 // 1 = sc0, 2 = nt, 16 = sc1).  Source rows and outputs are touched once:
@@ -136,8 +155,6 @@ __device__ __forceinline__ float normalize_f(const ChanNorm& c, float x) {
     return normalize_value(x, c.mean, c.stdv);
 }
 
-// ---- u8 bilinear fixed point (k_resize_direct.hip, k_yuv_resize.hip) ----
-
 // ---- LDS-DMA (buffer_load ... lds) bookkeeping (k_warp_frames.hip, k_resize_strip.hip) ----
 
 typedef __attribute__((address_space(3))) void lds_void;
@@ -164,19 +181,58 @@ __device__ __forceinline__ void wait_vm(int n) {
 // s_waitcnt lgkmcnt(0) alone
 __device__ __forceinline__ void wait_lgkm() { __builtin_amdgcn_s_waitcnt(0xF | (3 << 14) | (7 << 4)); }
 
-typedef unsigned short us2 __attribute__((ext_vector_type(2)));
+// ---- u8 bilinear fixed point ----
+
+// Byte k of the left tap and byte k of the right tap (byte CC + k) of the
+// tap bytes (lo, hi) as two u16 lanes: one v_perm_b32
+template <int CC>
+__device__ __forceinline__ uint32_t tap_pair(uint32_t lo, uint32_t hi, int k) {
+    const uint32_t sel = (uint32_t)k | (0x0Cu << 8) | ((uint32_t)(CC + k) << 16) | (0x0Cu << 24);
+    return __builtin_amdgcn_perm(hi, lo, sel);
+}
+
+// (tl*a0 + tr*a1)*wA + (bl*a0 + br*a1)*wB from a channel's packed tap pairs:
+// the reference's int32 sum (terms >= 0, total <= 255*2049^2 < 2^31), as one
+// packed u16 dot product per row (v_dot2_u32_u16) and two full-rate 24-bit
+// multiplies, both exact.  The u8 value is bits 22..29.
+__device__ __forceinline__ uint32_t blend_rows(uint32_t top, uint32_t bot, us2 wx, uint32_t wA, uint32_t wB) {
+    const uint32_t ht = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, top), wx, 0u, false);
+    const uint32_t hb = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, bot), wx, 0u, false);
+    return __umul24(ht, wA) + __umul24(hb, wB);
+}
+
+// The warp samplers' 11-bit weight of a tap fraction a in [0, 1):
+// SATURATE_CAST_SHORT of a value in (0, 2048]: the +0.5f branch, no clamp
+__device__ __forceinline__ int warp_weight(float a) { return (int)((1.f - a) * 2048.f + 0.5f); }
+
+// the channels' values (bits 24..31 of vh[k]) as the pixel's CC bytes
+template <int CC>
+__device__ __forceinline__ uint32_t pack_hi(const uint32_t (&vh)[CC]) {
+    if constexpr (CC == 1) return vh[0] >> 24;
+    else if constexpr (CC == 2) return __builtin_amdgcn_perm(vh[1], vh[0], 0x0C0C0703u);
+    else if constexpr (CC == 3)
+        return __builtin_amdgcn_perm(vh[2], __builtin_amdgcn_perm(vh[1], vh[0], 0x0C0C0703u), 0x0C070100u);
+    else
+        return __builtin_amdgcn_perm(__builtin_amdgcn_perm(vh[3], vh[2], 0x0C0C0703u),
+                                     __builtin_amdgcn_perm(vh[1], vh[0], 0x0C0C0703u), 0x05040100u);
+}
+
+// A u8-valued result v as the output element: the byte itself (kOutSame), its
+// float (kOutF32) or its normalised float (kOutNorm)
+template <int OUT, typename TOut>
+__device__ __forceinline__ TOut emit_u8(const ChanNorm& c, int v) {
+    if constexpr (OUT == kOutSame) return (TOut)v;
+    else if constexpr (OUT == kOutF32) return (TOut)(float)v;
+    else return (TOut)normalize_u8v(c, v);
+}
 
 // One channel of one output pixel from its packed tap pairs.  A zero weight
 // contributes exactly 0 in both formulas, so a skipped row is bot = 0, wB = 0.
 template <int MODE>
 __device__ __forceinline__ int blend_fixed(uint32_t top, uint32_t bot, us2 wx, uint32_t wA, uint32_t wB) {
+    if (MODE == VACV_LINEAR_REFERENCE) return (int)((blend_rows(top, bot, wx, wA, wB) >> 22) & 0xFFu);
     const uint32_t ht = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, top), wx, 0u, false);
     const uint32_t hb = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, bot), wx, 0u, false);
-    if (MODE == VACV_LINEAR_REFERENCE) {
-        // (tl*a0 + tr*a1)*wA + (bl*a0 + br*a1)*wB: the reference's int32 sum
-        // (terms >= 0, total <= 255*2049^2 < 2^31), 24-bit multiplies exact
-        return (int)(((__umul24(ht, wA) + __umul24(hb, wB)) >> 22) & 0xFFu);
-    }
     const int h0 = (int)(short)(ht >> 4);
     const int h1 = (int)(short)(hb >> 4);
     return clamp_u8((((h0 * (int)wA) >> 16) + ((h1 * (int)wB) >> 16) + 2) >> 2);
@@ -197,6 +253,7 @@ __device__ __forceinline__ FixedTap tap_of(int d, int n_in, int n_out, float sca
     r.i = t.i;
     // sat_short_away of a value in [0, 2048]: the clamp and the sign test
     // are no-ops (t.f is in [0, 1])
+    // (written out, not warp_weight: w1 is rounded on its own here, not 2048 - w0)
     r.w0 = (int)((1.f - t.f) * 2048.f + 0.5f);
     r.w1 = (int)(t.f * 2048.f + 0.5f);
     return r;
@@ -217,8 +274,8 @@ __device__ __forceinline__ void warp_border_sample(const unsigned char* sp, int6
     const TIn* r0 = reinterpret_cast<const TIn*>(sp + (int64_t)border_index(iy, h, mode) * rp);
     const TIn* r1 = reinterpret_cast<const TIn*>(sp + (int64_t)border_index(iy + 1, h, mode) * rp);
     if constexpr (std::is_same<TIn, uint8_t>::value) {
-        const int wy0 = (int)((1.f - ay) * 2048.f + 0.5f), wy1 = 2048 - wy0;
-        const int wx0 = (int)((1.f - ax) * 2048.f + 0.5f), wx1 = 2048 - wx0;
+        const int wy0 = warp_weight(ay), wy1 = 2048 - wy0;
+        const int wx0 = warp_weight(ax), wx1 = 2048 - wx0;
 #pragma unroll
         for (int k = 0; k < CC; ++k)
             vi[k] = ((int)r0[x0 + k] * wx0 * wy0 + (int)r1[x0 + k] * wx0 * wy1 + (int)r0[x1 + k] * wx1 * wy0 +
@@ -253,6 +310,55 @@ __device__ __forceinline__ uint32_t quad_pack(uint32_t own, int k) {
     } else {
         const uint32_t t = own | ((uint32_t)__builtin_amdgcn_mov_dpp((int)own, 0xF9, 0xF, 0xF, false) << 8);
         return (t & 0xFFFFu) | ((uint32_t)__builtin_amdgcn_mov_dpp((int)t, 0xFE, 0xF, 0xF, false) << 16);
+    }
+}
+
+// ---- a wave's LDS buffer to memory (each lane a 16-byte chunk per step) ----
+
+// vbytes bytes at xs to the tile row at drow: 16-byte non-temporal chunks with
+// a byte tail, bytes throughout for a misaligned row
+__device__ __forceinline__ void store_row_from_lds(unsigned char* drow, const unsigned char* xs, int vbytes, int lane) {
+    if ((reinterpret_cast<uintptr_t>(drow) & 15) == 0) {  // uniform
+        for (int c = lane; c * 16 < vbytes; c += 64) {
+            if (c * 16 + 16 <= vbytes) {
+                __builtin_nontemporal_store(*reinterpret_cast<const u32x4*>(xs + 16 * c),
+                                            reinterpret_cast<u32x4*>(drow) + c);
+            } else {
+                for (int e = c * 16; e < vbytes; ++e) drow[e] = xs[e];
+            }
+        }
+    } else {
+        for (int e = lane; e < vbytes; e += 64) drow[e] = xs[e];
+    }
+}
+
+// vbytes bytes at xs to the dense bytes [b0, b0 + vbytes) of the plane at dp:
+// dense byte b lives at row b / out_row, column byte b % out_row of rows rowp
+// bytes apart.  `chunked`: 16-byte chunks never straddle rows.
+__device__ __forceinline__ void store_range_from_lds(unsigned char* dp, const unsigned char* xs, uint32_t b0,
+                                                     uint32_t vbytes, uint32_t out_row, uint32_t rowp, bool dense,
+                                                     bool chunked, uint32_t lane) {
+    if (chunked) {
+        for (uint32_t c = lane; c * 16 < vbytes; c += 64) {
+            const uint32_t b = b0 + 16 * c;
+            uint32_t off = b;
+            if (!dense) {
+                const uint32_t r = b / out_row;
+                off = r * rowp + (b - r * out_row);
+            }
+            if (c * 16 + 16 <= vbytes) {
+                __builtin_nontemporal_store(*reinterpret_cast<const u32x4*>(xs + 16 * c),
+                                            reinterpret_cast<u32x4*>(dp + off));
+            } else {
+                for (uint32_t e = c * 16; e < vbytes; ++e) dp[off + (e - c * 16)] = xs[e];
+            }
+        }
+    } else {
+        for (uint32_t e = lane; e < vbytes; e += 64) {
+            const uint32_t b = b0 + e;
+            const uint32_t r = b / out_row;
+            dp[(int64_t)r * rowp + (b - r * out_row)] = xs[e];
+        }
     }
 }
 

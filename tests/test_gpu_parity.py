@@ -1352,13 +1352,20 @@ def test_warp_kernels_agree(ops, dev, oracle):
                             f"gather PX={px} norm"
     for c in (1, 2, 3, 4):  # every pixel width, odd sizes, both kernels vs the oracle
         im = synthetic_image(90 + c, 97, 143, c)
+        mean_c = np.array([103.94, 116.78, 123.68, 1.0][:c], np.float32)
+        std_c = np.array([57.375, 57.12, 58.395, 2.0][:c], np.float32)
         for m in mats[:2] + mats[3:4]:
             for wo in (121, 128):  # byte stores / the aligned 4-pixel stores, partial tiles
                 want = oracle.warp_affine(im, m, wo, 83).reshape(83, wo, c)
+                wantn = oracle.normalize(oracle.u8_to_f32(want), mean_c, std_c)
                 for flag in (4, 2, 0):
                     with ops.tuning(WARP_KERNEL=flag):
                         got = host(ops.warp_affine(to_dev(im.reshape(1, 97, 143, c), dev), m, wo, 83))[0]
+                        gotn = host(ops.warp_affine_normalize(to_dev(im.reshape(1, 97, 143, c), dev), m, wo, 83,
+                                                              mean_c, std_c))[0] if flag != 4 else None
                     assert_same(got.reshape(83, wo, c), want, f"warp c={c} {wo} kernel={flag}")
+                    if flag != 4:  # the gather kernels' fused normalisation at every pixel width
+                        assert_same(gotn.reshape(83, wo, c), wantn, f"warp normalize c={c} {wo} kernel={flag}")
     chw = to_dev(np.ascontiguousarray(imgs.transpose(0, 3, 1, 2)), dev)
     got = host(ops.warp_affine(chw, mats[0], 300, 200, layout=NCHW))
     for k in range(3):

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""tools/kbench.py against another build of libvacv_hip.so (diagnosis builds,
-e.g. `make LIB=lib_dbg1 OBJ=build_dbg1 EXTRA=-DVACV_FRAMES_DBG=1`):
+"""tools/kbench.py against another build of libvacv_hip.so (A/B builds,
+e.g. `make LIB=lib_ab OBJ=build_ab EXTRA=-DVACV_STRIP_AUX=2`):
   python tools/kbench_lib.py <dir with libvacv_hip.so> <kbench args...>"""
 import runpy
 import sys
