@@ -669,7 +669,9 @@ int fused_normalize(const vacv_image* dst_d, const float* mean, const float* std
     NormSpec ns;
     if ((st = norm_spec(dst, mean, stddev, ns))) return st;
     if (ns.mode == 1) return pass(ctx, kOutNorm, &ns, s);
-    // auto statistics: raw fp32 result, per-image stats of it, normalize in place
+    // auto statistics: raw fp32 result, per-image stats of it, normalize in place.
+    // What per_image_stats refuses is refused here, before the first pass writes dst.
+    if ((dst.layout == VACV_NHWC && dst.c > 4) || !dense(dst)) return VACV_ERR_UNSUPPORTED;
     if ((st = pass(ctx, kOutF32, nullptr, s))) return st;
     float *dm = nullptr, *ds = nullptr;
     if ((st = per_image_stats(dst, s, &dm, &ds))) return st;

@@ -255,7 +255,11 @@ int vacv_mean_stddev(const vacv_image* src, float* mean, float* stddev, void* st
  * resize, convert to fp32, normalize -- one pass, dst FP32.  Identical to
  * vacv_resize followed by vacv_normalize (u8 resize results are normalized
  * exactly as the reference normalizes a converted u8 tensor).  NULL mean and
- * stddev: per-image statistics of the resized image. */
+ * stddev: per-image statistics of the resized image; with NULL mean and
+ * stddev dst must be dense (no row, plane or batch padding) and NHWC dst at
+ * most 4 channels, or the call is VACV_ERR_UNSUPPORTED and writes nothing.
+ * The same holds for vacv_warp_affine_normalize, vacv_cvt_color_normalize and
+ * vacv_cvt_color_resize_normalize. */
 int vacv_resize_normalize(const vacv_image* src, const vacv_image* dst, int interpolation, int mode,
                           const float* mean, const float* stddev, void* stream);
 
@@ -330,7 +334,10 @@ int vacv_cvt_color_normalize(const vacv_image* src, const vacv_image* dst, int c
  * interpolation must be INTER_LINEAR.
  *  vacv_cvt_color_resize:           dst INT8 (u8 BGR/RGB) or FP32 (widened)
  *  vacv_cvt_color_resize_normalize: dst FP32; NULL mean and stddev = per-image
- *                                   statistics of the resized image. */
+ *                                   statistics of the resized image; with NULL
+ *                                   mean and stddev dst must be dense
+ *                                   (VACV_ERR_UNSUPPORTED otherwise, nothing
+ *                                   written). */
 int vacv_cvt_color_resize(const vacv_image* src, const vacv_image* dst, int code, int interpolation,
                           int mode, void* stream);
 int vacv_cvt_color_resize_normalize(const vacv_image* src, const vacv_image* dst, int code, int interpolation,
