@@ -21,65 +21,11 @@
 // bytes singly).  Pitched ROIs go row by row through the same copy.
 #pragma clang fp contract(off)
 
+#include "roi_tile.hpp"
 #include "vacv_device.hpp"
 
 namespace vacv {
 namespace {
-
-constexpr int kRoiPx = 4;                // 64-pixel gathers per wave
-constexpr int kRoiTile = kBlock * kRoiPx;  // pixels per workgroup
-
-// p / w and p % w for p < w + kRoiTile, w <= 2^20 (rw = 1.f / w): the float
-// quotient is within one of the true one, the remainder test settles it
-__device__ __forceinline__ void divmod_w(uint32_t p, uint32_t w, float rw, int& q, int& r) {
-    int qq = (int)((float)p * rw);
-    int rr = (int)p - qq * (int)w;
-    if (rr < 0) { --qq; rr += (int)w; }
-    else if (rr >= (int)w) { ++qq; rr -= (int)w; }
-    q = qq;
-    r = rr;
-}
-
-__device__ __forceinline__ float uniform_f(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
-}
-
-// nbytes from LDS offset `lo` of xch (16-byte aligned) to d, by threads t of
-// nt: 16-byte stores where LDS offset and destination agree modulo 16,
-// dwords where they agree modulo 4, else bytes; heads and tails bytewise.
-// The loops stay rolled: a band is at most a few 16-byte chunks per thread,
-// and the unrolled copies held the kernel at half of warp_kernel's occupancy.
-__device__ __forceinline__ void copy_run(unsigned char* d, const unsigned char* xch, uint32_t lo, int nbytes, int t,
-                                         int nt) {
-    const uintptr_t da = reinterpret_cast<uintptr_t>(d);
-    const unsigned char* xs = xch + lo;
-    const uint32_t diff = ((uint32_t)da ^ lo);
-    if ((diff & 15u) == 0) {  // uniform per run
-        const int head = min(nbytes, (int)((16u - ((uint32_t)da & 15u)) & 15u));
-        const int nmid = (nbytes - head) >> 4;
-#pragma unroll 1
-        for (int e = t; e < head; e += nt) d[e] = xs[e];
-#pragma unroll 1
-        for (int c = t; c < nmid; c += nt)
-            __builtin_nontemporal_store(*reinterpret_cast<const u32x4*>(xs + head + 16 * c),
-                                        reinterpret_cast<u32x4*>(d + head) + c);
-#pragma unroll 1
-        for (int e = head + 16 * nmid + t; e < nbytes; e += nt) d[e] = xs[e];
-    } else if ((diff & 3u) == 0) {
-        const int head = min(nbytes, (int)((4u - ((uint32_t)da & 3u)) & 3u));
-        const int nmid = (nbytes - head) >> 2;
-#pragma unroll 1
-        for (int e = t; e < head; e += nt) d[e] = xs[e];
-#pragma unroll 1
-        for (int c = t; c < nmid; c += nt)
-            reinterpret_cast<uint32_t*>(d + head)[c] = *reinterpret_cast<const uint32_t*>(xs + head + 4 * c);
-#pragma unroll 1
-        for (int e = head + 4 * nmid + t; e < nbytes; e += nt) d[e] = xs[e];
-    } else {
-#pragma unroll 1
-        for (int e = t; e < nbytes; e += nt) d[e] = xs[e];
-    }
-}
 
 // N consecutive floats at buffer byte offset `off`, one range-checked dword
 // load each (the compiler merges neighbours where it can prove it may)

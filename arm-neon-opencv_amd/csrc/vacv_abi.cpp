@@ -482,6 +482,15 @@ int warp_impl(const vacv_image* src_d, const vacv_image* dst_d, const float m[6]
     return hip_status(launch_warp(L, s));
 }
 
+// The ROI entry points' sampler options: INTER_LINEAR, optionally
+// WARP_INVERSE_MAP; every border mode but TRANSPARENT
+int rois_options(int flags, int border_mode) {
+    if (flags & ~(7 | VACV_WARP_INVERSE_MAP)) return VACV_ERR_UNSUPPORTED;
+    if ((flags & 7) != VACV_INTER_LINEAR) return VACV_ERR_UNSUPPORTED;
+    if (border_mode < VACV_BORDER_CONSTANT || border_mode >= VACV_BORDER_TRANSPARENT) return VACV_ERR_UNSUPPORTED;
+    return VACV_OK;
+}
+
 // vacv_warp_affine_rois[_normalize]: dst image i = warp of src image
 // src_index[i] under m[i].  m and src_index are device arrays: validated for
 // presence only, never read here.  ns: host-constant statistics (fp32 output,
@@ -496,9 +505,7 @@ int warp_rois_impl(const vacv_image* src_d, const vacv_image* dst_d, const float
     if (!src_index && src.n != 1 && src.n != dst.n) return VACV_ERR_INVALID_ARG;
     if (src.dtype != VACV_INT8 && src.dtype != VACV_FP32) return VACV_ERR_UNSUPPORTED;
     if (src.layout != VACV_NHWC) return VACV_ERR_UNSUPPORTED;
-    if (flags & ~(7 | VACV_WARP_INVERSE_MAP)) return VACV_ERR_UNSUPPORTED;
-    if ((flags & 7) != VACV_INTER_LINEAR) return VACV_ERR_UNSUPPORTED;
-    if (border_mode < VACV_BORDER_CONSTANT || border_mode >= VACV_BORDER_TRANSPARENT) return VACV_ERR_UNSUPPORTED;
+    if ((st = rois_options(flags, border_mode))) return st;
     if (src.c > 4) return VACV_ERR_UNSUPPORTED;
     if (src.w < 2 || src.h < 2) return VACV_ERR_INVALID_ARG;
     if (dst.dtype != (ns ? VACV_FP32 : src.dtype)) return VACV_ERR_INVALID_ARG;
@@ -657,6 +664,52 @@ int yuv_resize_impl(const vacv_image* src_d, const vacv_image* dst_d, int code, 
     L.scale_yd = (double)L.h / (double)L.ho;
     if (ns) L.norm = *ns;
     return hip_status(launch_yuv_resize(L, s));
+}
+
+// vacv_cvt_color_warp_affine_rois[_normalize]: dst image i = the ROI warp of
+// the decoded frame src_index[i] under m[i] (k_yuv_rois.hip).  src as
+// vacv_cvt_color's naive codes take it, m / src_index / flags / border as
+// warp_rois_impl: device arrays, validated for presence only.  ns:
+// host-constant statistics (fp32 output, NHWC or planar), or null (u8 NHWC).
+int yuv_rois_impl(const vacv_image* src_d, const vacv_image* dst_d, int code, const float* m,
+                  const int32_t* src_index, int flags, int border_mode, const double bv[4], const NormSpec* ns,
+                  hipStream_t s) {
+    Img src, dst;
+    int st = load2(src_d, dst_d, src, dst);
+    if (st) return st;
+    if (!m) return VACV_ERR_INVALID_ARG;
+    int v_first, rgb;
+    if ((st = color_code(code, v_first, rgb))) return st;
+    if (src.dtype != VACV_INT8 || src.c != 1 || src.layout != VACV_NHWC) return VACV_ERR_INVALID_ARG;
+    const int h = src.h / 3 * 2;  // cvt_color.cpp:152
+    if (src.w % 2 || h % 2 || h < 2 || src.h != h / 2 * 3) return VACV_ERR_INVALID_ARG;
+    if (dst.c != 3) return VACV_ERR_INVALID_ARG;
+    if (!src_index && src.n != 1 && src.n != dst.n) return VACV_ERR_INVALID_ARG;
+    if ((st = rois_options(flags, border_mode))) return st;
+    if (dst.dtype != (ns ? VACV_FP32 : VACV_INT8)) return VACV_ERR_INVALID_ARG;
+    if (!ns && dst.layout != VACV_NHWC) return VACV_ERR_INVALID_ARG;  // decoded frames are NHWC
+    YuvRoisLaunch L{};
+    L.src = src.data;
+    L.src_img = src.batch;
+    L.src_row = src.row;
+    L.src_bytes = src.row * (src.h - 1) + src.w;
+    if (L.src_bytes > kMaxPlaneBytes) return VACV_ERR_UNSUPPORTED;
+    L.dst = geom(dst);
+    L.n_src = src.n;
+    L.n_roi = dst.n;
+    L.w = src.w;
+    L.h = h;
+    L.m = m;
+    L.src_index = src_index;
+    L.inverse_map = (flags & VACV_WARP_INVERSE_MAP) != 0;
+    border_values(src, bv, L.border);
+    L.border_mode = border_mode;
+    L.v_first = v_first;
+    L.rgb = rgb;
+    L.out = ns ? kOutNorm : kOutSame;
+    L.planar = dst.layout == VACV_NCHW;
+    if (ns) L.norm = *ns;
+    return hip_status(launch_yuv_rois(L, s));
 }
 
 // Shape of the fp32 output viewed as its own image (for the auto-stats passes).
@@ -1047,6 +1100,28 @@ int vacv_cvt_color_resize_normalize(const vacv_image* src, const vacv_image* dst
                                     int mode, const float* mean, const float* stddev, void* stream) {
     YuvResizeCtx c{src, dst, code, interpolation, mode};
     return fused_normalize(dst, mean, stddev, (hipStream_t)stream, yuv_resize_pass, &c);
+}
+
+int vacv_cvt_color_warp_affine_rois(const vacv_image* src, const vacv_image* dst, int code, const float* m,
+                                    const int32_t* src_index, int flags, int border_mode,
+                                    const double border_value[4], void* stream) {
+    return yuv_rois_impl(src, dst, code, m, src_index, flags, border_mode, border_value, nullptr,
+                         (hipStream_t)stream);
+}
+
+int vacv_cvt_color_warp_affine_rois_normalize(const vacv_image* src, const vacv_image* dst, int code, const float* m,
+                                              const int32_t* src_index, int flags, int border_mode,
+                                              const double border_value[4], const float* mean, const float* stddev,
+                                              void* stream) {
+    if (!mean && !stddev) return VACV_ERR_UNSUPPORTED;  // per-image statistics of a ROI: not built
+    if (!mean || !stddev) return VACV_ERR_INVALID_ARG;
+    Img sm, d;
+    int st = load2(src, dst, sm, d);
+    if (st) return st;
+    if (d.c != 3) return VACV_ERR_INVALID_ARG;  // mean / stddev hold the decoded frame's 3 values
+    NormSpec ns;
+    if ((st = norm_spec(d, mean, stddev, ns))) return st;
+    return yuv_rois_impl(src, dst, code, m, src_index, flags, border_mode, border_value, &ns, (hipStream_t)stream);
 }
 
 int vacv_match_template(const vacv_image* img_d, const vacv_image* tpl_d, const vacv_image* res_d, int method,

@@ -318,6 +318,29 @@ struct YuvResizeLaunch {
 };
 hipError_t launch_yuv_resize(const YuvResizeLaunch& L, hipStream_t s);
 
+// Many crops of YUV420sp frames in one launch (k_yuv_rois.hip): ROI i =
+// cvt_color of frame src_index[i], then the ROI warp under m[i]; both arrays
+// are device memory read by the kernel
+struct YuvRoisLaunch {
+    const unsigned char* src;      // Y plane of frame 0
+    int64_t src_img, src_row;      // bytes
+    int64_t src_bytes;             // readable bytes of one frame (Y + chroma rows)
+    PlaneGeom dst;                 // ROI 0; img_pitch between ROIs; planar: plane_pitch between channel planes
+    int n_src, n_roi;
+    int w, h;                      // decoded frame size
+    const float* m;                // device [n_roi][6]
+    const int32_t* src_index;      // device [n_roi], or null: frame 0 (n_src == 1) or frame i
+    int inverse_map;               // m[i] is already the dst -> src map
+    float border[4];               // in the decoded channel order
+    int border_mode;               // kBorder* but TRANSPARENT
+    int v_first;                   // NV21
+    int rgb;                       // swap output channel order
+    int out;                       // kOutSame (u8 NHWC) or kOutNorm
+    int planar;                    // fp32 NCHW destination
+    NormSpec norm;
+};
+hipError_t launch_yuv_rois(const YuvRoisLaunch& L, hipStream_t s);
+
 struct NormLaunch {                // elementwise normalize
     PlaneGeom src;
     PlaneGeom dst;

@@ -369,10 +369,16 @@ struct SyncOnExit {
 // One launch for all crops: the frame and the matrices go to HBM once (host
 // operands through the pinned pool, device operands stay where they are), the
 // kernel writes the crops back to back into scratch, and each crop is copied
-// into its own dst tensor (placement of src).
+// into its own dst tensor (placement of src).  yuv_code != 0: src is a YUV420sp
+// frame and the crops are taken from its decoded (w, h, 3) image
+// (vacv_cvt_color_warp_affine_rois).
 void warp_rois_into(const char* fn, const Tensor& src, std::vector<Tensor>& dst, const std::vector<Tensor>& M,
-                    VSize dsize, int flags, int borderMode, const VScalar& bv, const Stats* stats) {
+                    VSize dsize, int flags, int borderMode, const VScalar& bv, const Stats* stats, int yuv_code = 0) {
     if (src.empty()) fail(fn, "empty input tensor");
+    if (yuv_code) {
+        check_yuv_code(fn, yuv_code);
+        (void)yuv_rows(fn, src);
+    }
     if (src.dtype != INT8 && src.dtype != FP32) fail(fn, "warp_affine takes INT8 or FP32");
     if (src.layout != NHWC) fail(fn, "the crops of one frame take an NHWC frame");
     if ((flags & ~(INTER_MAX | WARP_INVERSE_MAP)) || (flags & INTER_MAX) != INTER_LINEAR)
@@ -382,7 +388,8 @@ void warp_rois_into(const char* fn, const Tensor& src, std::vector<Tensor>& dst,
     if (M.empty()) fail(fn, "empty matrix list");
     const size_t n = M.size();
     const DType odt = stats ? FP32 : src.dtype;
-    const size_t roi_bytes = (size_t)dsize.w * dsize.h * src.c * dtype_size(odt);
+    const int oc = yuv_code ? 3 : src.c;
+    const size_t roi_bytes = (size_t)dsize.w * dsize.h * oc * dtype_size(odt);
     if (n > 0x7FFFFFFFu) fail(fn, "too many matrices");
     detail::Lease lease(detail::compute_device(src));
     for (const Tensor& m : M) {
@@ -417,18 +424,23 @@ void warp_rois_into(const char* fn, const Tensor& src, std::vector<Tensor>& dst,
     dd.n = (int)n;
     dd.w = dsize.w;
     dd.h = dsize.h;
-    dd.c = src.c;
+    dd.c = oc;
     dd.dtype = odt;
     dd.layout = NHWC;
     const double border[4] = {bv.v0, bv.v1, bv.v2, bv.v3};
-    if (stats)
+    if (yuv_code && stats)
+        detail::check(fn, vacv_cvt_color_warp_affine_rois_normalize(&sd, &dd, yuv_code, dm, nullptr, flags, borderMode,
+                                                                    border, stats->m(), stats->s(), s));
+    else if (yuv_code)
+        detail::check(fn, vacv_cvt_color_warp_affine_rois(&sd, &dd, yuv_code, dm, nullptr, flags, borderMode, border, s));
+    else if (stats)
         detail::check(fn, vacv_warp_affine_rois_normalize(&sd, &dd, dm, nullptr, flags, borderMode, border, stats->m(),
                                                           stats->s(), s));
     else
         detail::check(fn, vacv_warp_affine_rois(&sd, &dd, dm, nullptr, flags, borderMode, border, s));
     dst.resize(n);
     for (size_t i = 0; i < n; ++i) {
-        dst[i].create_on(src.device(), dsize.w, dsize.h, src.c, odt, NHWC);
+        dst[i].create_on(src.device(), dsize.w, dsize.h, oc, odt, NHWC);
         if (roi_bytes > 0 && !dst[i].data) fail(fn, "out of memory creating the output tensor");
         detail::check_hip(fn, hipMemcpyAsync(dst[i].data, dout + i * roi_bytes, roi_bytes,
                                              dst[i].on_device() ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
@@ -450,6 +462,20 @@ void warp_affine_normalize(const Tensor& src, std::vector<Tensor>& dst, const st
     const Stats stats = read_stats(fn, mean, stddev, src.c, false);
     if (!stats.m()) fail(fn, "the crops of one frame need mean and stddev (no per-image statistics)");
     warp_rois_into(fn, src, dst, M, dsize, flags, borderMode, borderValue, &stats);
+}
+
+void cvt_color_warp_affine(const Tensor& yuv, std::vector<Tensor>& dst, const std::vector<Tensor>& M, int code,
+                           VSize dsize, int flags, int borderMode, const VScalar& borderValue) {
+    warp_rois_into("va_cv::cvt_color_warp_affine", yuv, dst, M, dsize, flags, borderMode, borderValue, nullptr, code);
+}
+
+void cvt_color_warp_affine_normalize(const Tensor& yuv, std::vector<Tensor>& dst, const std::vector<Tensor>& M,
+                                     int code, VSize dsize, int flags, int borderMode, const VScalar& borderValue,
+                                     const Tensor& mean, const Tensor& stddev) {
+    static const char* fn = "va_cv::cvt_color_warp_affine_normalize";
+    const Stats stats = read_stats(fn, mean, stddev, 3, false);
+    if (!stats.m()) fail(fn, "the crops of one frame need mean and stddev (no per-image statistics)");
+    warp_rois_into(fn, yuv, dst, M, dsize, flags, borderMode, borderValue, &stats, code);
 }
 
 void cvt_color(const std::vector<Tensor>& src, std::vector<Tensor>& dst, int code) {

@@ -218,6 +218,19 @@ void warp_affine_normalize(const vision::Tensor& src, std::vector<vision::Tensor
                            int borderMode = BORDER_CONSTANT, const VScalar& borderValue = VScalar(),
                            const vision::Tensor& mean = vision::Tensor(),
                            const vision::Tensor& stddev = vision::Tensor());
+/// The same crops straight from one YUV420sp frame (w, h*3/2, 1) INT8 NHWC,
+/// ONE kernel launch and no decoded frame: dst[i] = warp_affine(cvt_color(yuv,
+/// code), M[i], dsize), byte for byte, (w, h, 3) crops.  code: the NV21 / NV12
+/// -> BGR / RGB codes; borderValue in the decoded channel order.
+void cvt_color_warp_affine(const vision::Tensor& yuv, std::vector<vision::Tensor>& dst,
+                           const std::vector<vision::Tensor>& M, int code, VSize dsize, int flags = INTER_LINEAR,
+                           int borderMode = BORDER_CONSTANT, const VScalar& borderValue = VScalar());
+void cvt_color_warp_affine_normalize(const vision::Tensor& yuv, std::vector<vision::Tensor>& dst,
+                                     const std::vector<vision::Tensor>& M, int code, VSize dsize,
+                                     int flags = INTER_LINEAR, int borderMode = BORDER_CONSTANT,
+                                     const VScalar& borderValue = VScalar(),
+                                     const vision::Tensor& mean = vision::Tensor(),
+                                     const vision::Tensor& stddev = vision::Tensor());
 void cvt_color(const std::vector<vision::Tensor>& src, std::vector<vision::Tensor>& dst, int code);
 void cvt_color_normalize(const std::vector<vision::Tensor>& src, std::vector<vision::Tensor>& dst, int code,
                          const vision::Tensor& mean = vision::Tensor(),

@@ -12,12 +12,14 @@ from ._lib import (BORDER_CONSTANT, BORDER_REFLECT, BORDER_REFLECT_101, BORDER_R
                    FP16, FP32, FP64, INT8, INTER_AREA, INTER_CUBIC, INTER_LANCZOS4, INTER_LINEAR, INTER_NEAREST, LINEAR_NEON, LINEAR_OPENCV,
                    LINEAR_REFERENCE, NCHW, NHWC, WARP_INVERSE_MAP, VacvError, build)
 
-__all__ = ["ops", "dist", "build", "VacvError"]
+__all__ = ["ops", "dist", "build", "VacvError", "cvt_color_warp_affine_rois", "cvt_color_warp_affine_rois_normalize"]
 
 
 def __getattr__(name):
     # ops/dist import torch; keep `import vacv_amd` cheap for build-only users
+    import importlib
     if name in ("ops", "dist"):
-        import importlib
         return importlib.import_module(f".{name}", __name__)
+    if name in ("cvt_color_warp_affine_rois", "cvt_color_warp_affine_rois_normalize"):  # ops', on first use
+        return getattr(importlib.import_module(".ops", __name__), name)
     raise AttributeError(name)

@@ -417,6 +417,47 @@ def cvt_color_resize_normalize(yuv: torch.Tensor, w: int, h: int, mean=None, std
     return out if yuv.dim() == 3 else out[0]
 
 
+def cvt_color_warp_affine_rois(yuv: torch.Tensor, ms, w: int, h: int, code: int = L.COLOR_YUV2BGR_NV21,
+                               src_index=None, flags: int = INTER_LINEAR, border_mode: int = BORDER_CONSTANT,
+                               border_value=(0, 0, 0, 0), out=None, stream=None) -> torch.Tensor:
+    """Many crops straight from NV21 / NV12 frames in one launch: out[i] =
+    warp_affine(cvt_color(yuv[src_index[i]], code), ms[i], w, h), byte for byte,
+    without the decoded frames.  yuv: (n, h_in*3/2, w_in) u8 frames or one
+    (h_in*3/2, w_in) frame; ms / src_index as warp_affine_rois takes them
+    (device tensors, read by the kernel when it runs on `stream`);
+    border_value in the decoded channel order.  Returns (n, h, w, 3) u8."""
+    y4 = yuv if yuv.dim() == 3 else yuv.unsqueeze(0)
+    _, ms, src_index, n = _rois_args(y4.unsqueeze(-1), ms, src_index)
+    if out is None:
+        out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=yuv.device)
+    bv, bp = _dptr((list(border_value) + [0, 0, 0, 0])[:4])  # the C side reads four
+    check("vacv_cvt_color_warp_affine_rois", L.load().vacv_cvt_color_warp_affine_rois(
+        ctypes.byref(_yuv_desc(y4)), ctypes.byref(describe(out, NHWC)), code, ms.data_ptr(),
+        src_index.data_ptr() if src_index is not None else None, flags, border_mode, bp, _stream(stream)))
+    return out
+
+
+def cvt_color_warp_affine_rois_normalize(yuv: torch.Tensor, ms, w: int, h: int, mean, std,
+                                         code: int = L.COLOR_YUV2BGR_NV21, src_index=None, layout: int = NHWC,
+                                         flags: int = INTER_LINEAR, border_mode: int = BORDER_CONSTANT,
+                                         border_value=(0, 0, 0, 0), out=None, stream=None) -> torch.Tensor:
+    """cvt_color_warp_affine_rois with the fused normalize: fp32 (n, h, w, 3),
+    or planar (n, 3, h, w) with layout=NCHW, the model-input layout."""
+    y4 = yuv if yuv.dim() == 3 else yuv.unsqueeze(0)
+    _, ms, src_index, n = _rois_args(y4.unsqueeze(-1), ms, src_index)
+    if mean is None or std is None:
+        raise ValueError("cvt_color_warp_affine_rois_normalize needs mean and stddev (no per-image statistics for ROIs)")
+    if out is None:
+        out = torch.empty((n, h, w, 3) if layout == NHWC else (n, 3, h, w), dtype=torch.float32, device=yuv.device)
+    bv, bp = _dptr((list(border_value) + [0, 0, 0, 0])[:4])  # the C side reads four
+    (ma, meanp), (sa, stdp) = _meanstd(mean, std, 3)
+    check("vacv_cvt_color_warp_affine_rois_normalize", L.load().vacv_cvt_color_warp_affine_rois_normalize(
+        ctypes.byref(_yuv_desc(y4)), ctypes.byref(describe(out, layout)), code, ms.data_ptr(),
+        src_index.data_ptr() if src_index is not None else None, flags, border_mode, bp, meanp, stdp,
+        _stream(stream)))
+    return out
+
+
 # ---------------------------------------------------------------------------
 # normalize / statistics
 

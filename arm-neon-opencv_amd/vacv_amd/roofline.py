@@ -120,18 +120,9 @@ def _clip_polygon(poly, w: float, h: float):
     return poly
 
 
-def warp_rois_bytes(w_in: int, h_in: int, c: int, w_out: int, h_out: int, ms, in_esize: int = 1,
-                    out_esize: int = 1, inverse_map: bool = False) -> int:
-    """B_alg of vacv_warp_affine_rois: the output bytes of every ROI plus the
-    bytes of each ROI's source parallelogram -- the image of the output
-    rectangle [0, w_out] x [0, h_out] under the dst -> src map -- clipped to
-    the frame [0, w_in] x [0, h_in] (its area rounded to whole pixels).  From
-    shapes and matrices alone, on the host, in float64; a singular or
-    non-finite map reads nothing.  Source pixels that two ROIs share are
-    counted for both: each ROI is its own launch-independent piece of work."""
-    ms = np.asarray(ms, dtype=np.float64).reshape(-1, 6)
-    total = ms.shape[0] * w_out * h_out * c * out_esize
-    for m in ms:
+def _roi_source_pixels(w_in: int, h_in: int, w_out: int, h_out: int, ms, inverse_map: bool):
+    """Per map: the whole pixels of the ROI's source parallelogram clipped to the frame."""
+    for m in np.asarray(ms, dtype=np.float64).reshape(-1, 6):
         if not np.all(np.isfinite(m)):
             continue
         if inverse_map:
@@ -148,5 +139,34 @@ def warp_rois_bytes(w_in: int, h_in: int, c: int, w_out: int, h_out: int, ms, in
         if len(poly) < 3:
             continue
         area = 0.5 * abs(sum(p[0] * q[1] - q[0] * p[1] for p, q in zip(poly, poly[1:] + poly[:1])))
-        total += int(round(area)) * c * in_esize
+        yield int(round(area))
+
+
+def yuv_warp_rois_bytes(w_in: int, h_in: int, w_out: int, h_out: int, ms, out_esize: int = 1,
+                        inverse_map: bool = False) -> int:
+    """B_alg of vacv_cvt_color_warp_affine_rois[_normalize]: the 3-channel
+    output of every ROI plus each ROI's clipped source parallelogram (as
+    warp_rois_bytes finds it, in the decoded w_in x h_in frame) at 1 byte per
+    pixel of Y and the chroma covering it at half a byte per pixel (one VU
+    pair per 2 x 2 pixels; an odd pixel count rounds the half byte up)."""
+    n = np.asarray(ms, dtype=np.float64).reshape(-1, 6).shape[0]
+    total = n * w_out * h_out * 3 * out_esize
+    for px in _roi_source_pixels(w_in, h_in, w_out, h_out, ms, inverse_map):
+        total += px + (px + 1) // 2
+    return int(total)
+
+
+def warp_rois_bytes(w_in: int, h_in: int, c: int, w_out: int, h_out: int, ms, in_esize: int = 1,
+                    out_esize: int = 1, inverse_map: bool = False) -> int:
+    """B_alg of vacv_warp_affine_rois: the output bytes of every ROI plus the
+    bytes of each ROI's source parallelogram -- the image of the output
+    rectangle [0, w_out] x [0, h_out] under the dst -> src map -- clipped to
+    the frame [0, w_in] x [0, h_in] (its area rounded to whole pixels).  From
+    shapes and matrices alone, on the host, in float64; a singular or
+    non-finite map reads nothing.  Source pixels that two ROIs share are
+    counted for both: each ROI is its own launch-independent piece of work."""
+    n = np.asarray(ms, dtype=np.float64).reshape(-1, 6).shape[0]
+    total = n * w_out * h_out * c * out_esize
+    for px in _roi_source_pixels(w_in, h_in, w_out, h_out, ms, inverse_map):
+        total += px * c * in_esize
     return int(total)

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define VACV_ABI_VERSION 4
+#define VACV_ABI_VERSION 5
 #define VACV_MAX_CHANNELS 16
 
 typedef enum vacv_status {
@@ -342,6 +342,39 @@ int vacv_cvt_color_resize(const vacv_image* src, const vacv_image* dst, int code
                           int mode, void* stream);
 int vacv_cvt_color_resize_normalize(const vacv_image* src, const vacv_image* dst, int code, int interpolation,
                                     int mode, const float* mean, const float* stddev, void* stream);
+
+/* The second stage of that pipeline: many crops straight from NV21 / NV12
+ * frames in one launch, without materialising the decoded frames.
+ * src: `src->n` YUV420sp frames as vacv_cvt_color takes them, (w, h*3/2, 1)
+ *      INT8, w and h even (>= 2), pitched (row and batch pitch) or dense, any
+ *      base alignment.
+ * code: VACV_COLOR_YUV2{BGR,RGB}_{NV21,NV12}; the codes of OpenCV's
+ *      arithmetic (RGBA/BGRA, YV12, GRAY2BGR): UNSUPPORTED.
+ * dst: `dst->n` ROIs of dst->w x dst->h, c = 3.
+ *      vacv_cvt_color_warp_affine_rois:           INT8 NHWC, dense or pitched
+ *      vacv_cvt_color_warp_affine_rois_normalize: FP32, NHWC or NCHW, dense or
+ *        pitched (row, plane and batch pitch); mean / stddev: host arrays of 3
+ *        floats, both required (one NULL: INVALID_ARG; both NULL: UNSUPPORTED).
+ * m, src_index, flags, border_mode: exactly as vacv_warp_affine_rois (DEVICE
+ * arrays read by the kernel at execution time, never dereferenced by the
+ * host; the same NULL-index rules; INTER_LINEAR [| VACV_WARP_INVERSE_MAP];
+ * TRANSPARENT: UNSUPPORTED).  border_value[0..2] are in the decoded channel
+ * order.
+ * ROI i is byte-identical to vacv_cvt_color(frame src_index[i], code)
+ * followed by vacv_warp_affine_rois[_normalize] on that decoded (w, h, 3)
+ * frame with m[i]; bytes of the dst allocation outside the ROI rectangles
+ * are never written.  The call copies nothing between host and device,
+ * allocates nothing and never synchronizes.  Device-supplied values cannot
+ * fault: every source read is range-checked by the hardware against the
+ * indexed frame's Y and chroma rows, and an index outside [0, src->n) gives
+ * a ROI of border_value in every border mode. */
+int vacv_cvt_color_warp_affine_rois(const vacv_image* src, const vacv_image* dst, int code,
+                                    const float* m, const int32_t* src_index, int flags, int border_mode,
+                                    const double border_value[4], void* stream);
+int vacv_cvt_color_warp_affine_rois_normalize(const vacv_image* src, const vacv_image* dst, int code,
+                                    const float* m, const int32_t* src_index, int flags, int border_mode,
+                                    const double border_value[4],
+                                    const float* mean, const float* stddev, void* stream);
 
 /* ---- template matching ------------------------------------------------ */
 

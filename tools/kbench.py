@@ -27,7 +27,8 @@ def main():
                          "e.g. 'DIRECT_ALIGN=0,1;RESIZE_WORK=2,4'")
     ap.add_argument("--compare", action="store_true",
                     help="--op warp_rois: time each one-call case against the same crops as a loop of single "
-                         "calls (vacv_warp_affine; vacv_warp_affine_normalize + one vacv_change_layout), alternating")
+                         "calls (vacv_warp_affine; vacv_warp_affine_normalize + one vacv_change_layout), alternating; "
+                         "--op yuv_rois: against vacv_cvt_color of all frames + vacv_warp_affine_rois[_normalize]")
     ap.add_argument("--baseline-lib", default="",
                     help="--compare: libvacv_hip.so of another build (e.g. the parent commit's) to run the loop on; "
                          "default: this build's own single-call entry points")
@@ -224,8 +225,54 @@ def main():
             warp_rois_bytes(1280, 720, 3, 140, 210, ms7), 64 * 140 * 210)
         loops["warp_rois_720p_64x140x210_u8"] = dict(src=src7, ms=ms7, idx=np.zeros(64, np.int32),
                                                      out=torch.empty_like(o7), norm=False)
+    chains = {}
+    if a.op in ("yuv_rois", "all"):
+        # the warp_rois cases with NV21 frames as the source
+        # (vacv_cvt_color_warp_affine_rois): the same seeded geometry
+        import numpy as np
+        from vacv_amd.roofline import yuv_warp_rois_bytes
+        rng = np.random.default_rng(20261019)
+
+        def yuv_roi_maps(n, fw, fh, wo, ho, foot=250.0):
+            ms = np.zeros((n, 6), np.float32)
+            for i in range(n):
+                ang, s = np.deg2rad(rng.uniform(-30.0, 30.0)), max(wo, ho) / foot
+                cx, cy = rng.uniform(0, fw), rng.uniform(0, fh)
+                ca, sa = s * np.cos(ang), s * np.sin(ang)
+                ms[i] = [ca, sa, wo / 2 - ca * cx - sa * cy, -sa, ca, ho / 2 + sa * cx - ca * cy]
+            return ms
+
+        yuv = torch.randint(0, 256, (8, 1620, 1920), dtype=torch.uint8, device=dev, generator=g)
+        ms = yuv_roi_maps(256, 1920, 1080, 112, 112)
+        idx = np.arange(256, dtype=np.int32) % 8
+        dms, didx = torch.from_numpy(ms).to(dev), torch.from_numpy(idx).to(dev)
+        o = torch.empty((256, 112, 112, 3), dtype=torch.uint8, device=dev)
+        cases["yuv_rois_1080p_256x112_u8"] = (
+            lambda yuv=yuv, dms=dms, didx=didx, o=o: ops.cvt_color_warp_affine_rois(yuv, dms, 112, 112, src_index=didx,
+                                                                                  out=o),
+            yuv_warp_rois_bytes(1920, 1080, 112, 112, ms), 256 * 112 * 112)
+        chains["yuv_rois_1080p_256x112_u8"] = dict(yuv=yuv, ms=dms, idx=didx, out=torch.empty_like(o), norm=False)
+        of = torch.empty((256, 3, 112, 112), dtype=torch.float32, device=dev)
+        cases["yuv_rois_normalize_1080p_256x112_chw"] = (
+            lambda yuv=yuv, dms=dms, didx=didx, of=of: ops.cvt_color_warp_affine_rois_normalize(
+                yuv, dms, 112, 112, MEAN, STD, src_index=didx, layout=vacv_amd.NCHW, out=of),
+            yuv_warp_rois_bytes(1920, 1080, 112, 112, ms, out_esize=4), 256 * 112 * 112)
+        chains["yuv_rois_normalize_1080p_256x112_chw"] = dict(yuv=yuv, ms=dms, idx=didx, out=torch.empty_like(of),
+                                                              norm=True)
+        # the reference harness's crop size: 64 crops of one 1280 x 720 frame
+        yuv7 = torch.randint(0, 256, (1, 1080, 1280), dtype=torch.uint8, device=dev, generator=g)
+        ms7 = yuv_roi_maps(64, 1280, 720, 140, 210)
+        dms7 = torch.from_numpy(ms7).to(dev)
+        o7 = torch.empty((64, 210, 140, 3), dtype=torch.uint8, device=dev)
+        cases["yuv_rois_720p_64x140x210_u8"] = (
+            lambda yuv7=yuv7, dms7=dms7, o7=o7: ops.cvt_color_warp_affine_rois(yuv7, dms7, 140, 210, out=o7),
+            yuv_warp_rois_bytes(1280, 720, 140, 210, ms7), 64 * 140 * 210)
+        chains["yuv_rois_720p_64x140x210_u8"] = dict(yuv=yuv7, ms=dms7, idx=None, out=torch.empty_like(o7), norm=False)
     if a.only:
         cases = {k: v for k, v in cases.items() if a.only in k}
+    if a.compare and a.op == "yuv_rois":
+        compare_with_chains({k: v for k, v in cases.items() if k in chains}, chains, a.baseline_lib, a.iters)
+        return
     if a.compare:
         compare_with_loops({k: v for k, v in cases.items() if k in loops}, loops, a.baseline_lib, a.iters)
         return
@@ -310,6 +357,90 @@ def compare_with_loops(cases, loops, baseline_lib, iters):
                           "one_call_ms_min": round(min(t_one), 4), "loop_over_one_call": round(ml / mo, 2),
                           "alg_bytes": int(nbytes), "one_call_alg_GBps": round(nbytes / mo / 1e6, 1),
                           "outputs_equal": same, "clock": "host, stream synchronised"}), flush=True)
+
+
+def compare_with_chains(cases, chains, baseline_lib, iters):
+    """--op yuv_rois: the one call against the chain it replaces -- vacv_cvt_color
+    of all frames into a BGR buffer, then vacv_warp_affine_rois[_normalize] on
+    it -- per case, both timed end to end with a host clock around a
+    synchronised stream, alternating, after warm-up; outputs compared equal.
+    The chain runs on `baseline_lib` (e.g. the parent commit's build) by its
+    own handle, or on this build.  Descriptors and ctypes references are built
+    beforehand for both legs, so what is timed is the library (the binding's
+    own argument handling is tens of microseconds, as much as either leg)."""
+    import ctypes
+    import time
+
+    import torch
+    import vacv_amd
+    from vacv_amd import _lib as L, ops
+    lib = L.load()
+    if baseline_lib:
+        base = ctypes.CDLL(str(Path(baseline_lib).resolve()))
+        for fname in ("vacv_cvt_color", "vacv_warp_affine_rois", "vacv_warp_affine_rois_normalize", "vacv_abi_version"):
+            getattr(base, fname).argtypes, getattr(base, fname).restype = L.SIGNATURES[fname]
+        tag = f"{baseline_lib} (ABI {base.vacv_abi_version()})"
+    else:
+        base, tag = lib, "this build"
+    stream = ops._stream()
+    bv = (ctypes.c_double * 4)(0, 0, 0, 0)
+    mean, std = (ctypes.c_float * 3)(*MEAN), (ctypes.c_float * 3)(*STD)
+    for name, (binding_call, nbytes, px) in cases.items():
+        ch = chains[name]
+        yuv, ms, idx, out, norm = ch["yuv"], ch["ms"], ch["idx"], ch["out"], ch["norm"]
+        bgr = torch.empty((yuv.shape[0], yuv.shape[1] // 3 * 2, yuv.shape[2], 3), dtype=torch.uint8, device=yuv.device)
+        yd, bd = ops._yuv_desc(yuv), ops.describe(bgr)
+        od = ops.describe(out, vacv_amd.NCHW if norm else vacv_amd.NHWC)
+        mp, ip = ms.data_ptr(), (idx.data_ptr() if idx is not None else None)
+
+        def chain():
+            assert base.vacv_cvt_color(ctypes.byref(yd), ctypes.byref(bd), L.COLOR_YUV2BGR_NV21, stream) == 0
+            if norm:
+                assert base.vacv_warp_affine_rois_normalize(ctypes.byref(bd), ctypes.byref(od), mp, ip, 1, 0, bv, mean, std,
+                                                            stream) == 0
+            else:
+                assert base.vacv_warp_affine_rois(ctypes.byref(bd), ctypes.byref(od), mp, ip, 1, 0, bv, stream) == 0
+
+        one = binding_call()  # the binding's own output tensor, written by the calls below
+        od1 = ops.describe(one, vacv_amd.NCHW if norm else vacv_amd.NHWC)
+
+        def fn():
+            if norm:
+                assert lib.vacv_cvt_color_warp_affine_rois_normalize(ctypes.byref(yd), ctypes.byref(od1),
+                                                                     L.COLOR_YUV2BGR_NV21, mp, ip, 1, 0, bv, mean, std,
+                                                                     stream) == 0
+            else:
+                assert lib.vacv_cvt_color_warp_affine_rois(ctypes.byref(yd), ctypes.byref(od1), L.COLOR_YUV2BGR_NV21, mp,
+                                                           ip, 1, 0, bv, stream) == 0
+
+        def timed(f):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            f()
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) * 1e3
+
+        one.zero_()
+        for _ in range(20):
+            chain()
+            fn()
+        torch.cuda.synchronize()
+        same = bool(torch.equal(one, out))  # both legs compute the same crops
+        t_chain, t_one = [], []
+        for _ in range(iters):
+            t_chain.append(timed(chain))
+            t_one.append(timed(fn))
+        t_chain.sort()
+        t_one.sort()
+        mc, mo = t_chain[iters // 2], t_one[iters // 2]
+        print(json.dumps({"case": name, "rois": int(ms.shape[0]), "frames": int(yuv.shape[0]), "baseline": tag,
+                          "chain_ms_median": round(mc, 4), "chain_ms_min": round(t_chain[0], 4),
+                          "chain_ms_p10": round(t_chain[iters // 10], 4), "chain_ms_p90": round(t_chain[iters * 9 // 10], 4),
+                          "one_call_ms_median": round(mo, 4), "one_call_ms_min": round(t_one[0], 4),
+                          "one_call_ms_p90": round(t_one[iters * 9 // 10], 4),
+                          "chain_over_one_call": round(mc / mo, 2), "alg_bytes": int(nbytes),
+                          "one_call_alg_GBps": round(nbytes / mo / 1e6, 1), "outputs_equal": same,
+                          "clock": "host, stream synchronised"}), flush=True)
 
 
 def run_cases(cases, iters, tag):
