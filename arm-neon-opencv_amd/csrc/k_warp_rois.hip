@@ -27,15 +27,6 @@
 namespace vacv {
 namespace {
 
-// N consecutive floats at buffer byte offset `off`, one range-checked dword
-// load each (the compiler merges neighbours where it can prove it may)
-template <int N>
-__device__ __forceinline__ void load_f32(const Rsrc& rs, uint32_t off, float (&v)[N]) {
-#pragma unroll
-    for (int i = 0; i < N; ++i)
-        v[i] = __builtin_bit_cast(float, (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs.r, (int)(off + 4u * i), 0, 0));
-}
-
 // PLANAR: fp32 NCHW destination (one LDS region and one byte range per plane)
 // EXT: border modes other than CONSTANT (a separate instance, as warp_kernel)
 template <int CC, typename TIn, int OUT, bool PLANAR, bool EXT>

@@ -1,5 +1,5 @@
 // roi_tile.hpp -- the tiling helpers of the ROI kernels (k_warp_rois.hip,
-// k_yuv_rois.hip): a workgroup owns kRoiTile consecutive row-major pixels of
+// k_yuv_rois.hip, k_crop_resize_rois.hip): a workgroup owns kRoiTile consecutive row-major pixels of
 // one ROI, lays its band out in LDS at the destination's offset modulo 16 and
 // copies it out in the widest stores the alignment allows.
 #pragma once
@@ -25,6 +25,15 @@ __device__ __forceinline__ void divmod_w(uint32_t p, uint32_t w, float rw, int& 
 
 __device__ __forceinline__ float uniform_f(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
+}
+
+// N consecutive floats at buffer byte offset `off`, one range-checked dword
+// load each (the compiler merges neighbours where it can prove it may)
+template <int N>
+__device__ __forceinline__ void load_f32(const Rsrc& rs, uint32_t off, float (&v)[N]) {
+#pragma unroll
+    for (int i = 0; i < N; ++i)
+        v[i] = __builtin_bit_cast(float, (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs.r, (int)(off + 4u * i), 0, 0));
 }
 
 // nbytes from LDS offset `lo` of xch (16-byte aligned) to d, by threads t of

@@ -530,6 +530,43 @@ int warp_rois_impl(const vacv_image* src_d, const vacv_image* dst_d, const float
     return hip_status(launch_warp_rois(L, s));
 }
 
+// vacv_crop_resize_rois[_normalize]: dst image i = rect rects[i] of src image
+// src_index[i], resized to dst->w x dst->h.  rects and src_index are device
+// arrays: validated for presence only, never read here.  ns as warp_rois_impl.
+int crop_resize_rois_impl(const vacv_image* src_d, const vacv_image* dst_d, const int32_t* rects,
+                          const int32_t* src_index, int interpolation, int mode, const NormSpec* ns, hipStream_t s) {
+    Img src, dst;
+    int st = load2(src_d, dst_d, src, dst);
+    if (st) return st;
+    if (!rects) return VACV_ERR_INVALID_ARG;
+    if (src.c != dst.c) return VACV_ERR_INVALID_ARG;
+    if (!src_index && src.n != 1 && src.n != dst.n) return VACV_ERR_INVALID_ARG;
+    if (src.dtype != VACV_INT8 && src.dtype != VACV_FP32) return VACV_ERR_UNSUPPORTED;
+    if (src.layout != VACV_NHWC) return VACV_ERR_UNSUPPORTED;
+    if (interpolation != VACV_INTER_LINEAR) return VACV_ERR_UNSUPPORTED;
+    if (src.c > 4) return VACV_ERR_UNSUPPORTED;
+    if (mode < VACV_LINEAR_REFERENCE || mode > VACV_LINEAR_OPENCV) return VACV_ERR_INVALID_ARG;
+    if (src.w < 2 || src.h < 2) return VACV_ERR_INVALID_ARG;  // resize_naive.cpp:28-31 needs 2 taps
+    if (dst.dtype != (ns ? VACV_FP32 : src.dtype)) return VACV_ERR_INVALID_ARG;
+    if (!ns && dst.layout != VACV_NHWC) return VACV_ERR_INVALID_ARG;  // dst layout = src's
+    // planar output: 3 channels; one channel is the same bytes either way
+    const bool planar = dst.layout == VACV_NCHW && dst.c > 1;
+    if (planar && dst.c != 3) return VACV_ERR_UNSUPPORTED;
+    CropResizeRoisLaunch L{};
+    L.src = geom(src);
+    L.dst = geom(dst);
+    L.n_src = src.n;
+    L.n_roi = dst.n;
+    L.rects = rects;
+    L.src_index = src_index;
+    L.mode = mode;
+    L.out = ns ? kOutNorm : kOutSame;
+    L.planar = planar;
+    if (ns) L.norm = *ns;
+    if (!crop_resize_rois_fits(L)) return VACV_ERR_UNSUPPORTED;
+    return hip_status(launch_crop_resize_rois(L, s));
+}
+
 int color_code(int code, int& v_first, int& rgb) {
     switch (code) {
         case VACV_COLOR_YUV2BGR_NV21: v_first = 1; rgb = 0; return VACV_OK;
@@ -943,6 +980,26 @@ int vacv_warp_affine_rois_normalize(const vacv_image* src, const vacv_image* dst
     NormSpec ns;
     if ((st = norm_spec(d, mean, stddev, ns))) return st;
     return warp_rois_impl(src, dst, m, src_index, flags, border_mode, border_value, &ns, (hipStream_t)stream);
+}
+
+int vacv_crop_resize_rois(const vacv_image* src, const vacv_image* dst, const int32_t* rects, const int32_t* src_index,
+                          int interpolation, int mode, void* stream) {
+    return crop_resize_rois_impl(src, dst, rects, src_index, interpolation, mode, nullptr, (hipStream_t)stream);
+}
+
+int vacv_crop_resize_rois_normalize(const vacv_image* src, const vacv_image* dst, const int32_t* rects,
+                                    const int32_t* src_index, int interpolation, int mode, const float* mean,
+                                    const float* stddev, void* stream) {
+    if (!mean && !stddev) return VACV_ERR_UNSUPPORTED;  // per-image statistics of a ROI: not built
+    if (!mean || !stddev) return VACV_ERR_INVALID_ARG;
+    Img sm, d;
+    int st = load(src, sm);
+    if (st) return st;
+    if ((st = load(dst, d))) return st;
+    if (sm.c != d.c) return VACV_ERR_INVALID_ARG;  // mean / stddev hold the source's c values
+    NormSpec ns;
+    if ((st = norm_spec(d, mean, stddev, ns))) return st;
+    return crop_resize_rois_impl(src, dst, rects, src_index, interpolation, mode, &ns, (hipStream_t)stream);
 }
 
 int vacv_warp_affine(const vacv_image* src, const vacv_image* dst, const float m[6], int flags, int border_mode,

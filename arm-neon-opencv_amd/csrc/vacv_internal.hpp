@@ -216,6 +216,22 @@ struct WarpRoisLaunch {
 };
 hipError_t launch_warp_rois(const WarpRoisLaunch& L, hipStream_t s);
 hipError_t launch_invert_affine(const float* m, float* inv, int n, hipStream_t s);
+// Many upright crops in one launch (k_crop_resize_rois.hip): ROI i = bilinear
+// resize of rect rects[i] of frame src_index[i] with the rect's own taps;
+// both arrays are device memory read by the kernel
+struct CropResizeRoisLaunch {
+    PlaneGeom src;               // NHWC frames (planes = 1)
+    PlaneGeom dst;               // ROI 0; img_pitch between ROIs; planar: plane_pitch between channel planes
+    int n_src, n_roi;
+    const int32_t* rects;        // device [n_roi][4]: left, top, width, height
+    const int32_t* src_index;    // device [n_roi], or null: frame 0 (n_src == 1) or frame i
+    int mode;                    // VACV_LINEAR_* (u8)
+    int out;                     // kOutSame or kOutNorm
+    int planar;                  // fp32 NCHW destination
+    NormSpec norm;
+};
+bool crop_resize_rois_fits(const CropResizeRoisLaunch& L);  // within the kernel's 32-bit indices
+hipError_t launch_crop_resize_rois(const CropResizeRoisLaunch& L, hipStream_t s);
 // u8 CONSTANT warp (1-4 interleaved channels, or NCHW planes) with the source boxes
 // copied into an LDS ring by LDS-DMA and the geometry shared by kf frames per
 // workgroup (k_warp_frames.hip)

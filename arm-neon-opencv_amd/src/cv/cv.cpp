@@ -478,6 +478,93 @@ void cvt_color_warp_affine_normalize(const Tensor& yuv, std::vector<Tensor>& dst
     warp_rois_into(fn, yuv, dst, M, dsize, flags, borderMode, borderValue, &stats, code);
 }
 
+// ---- one frame, many upright crops (vacv_crop_resize_rois) -----------------
+
+namespace {
+
+// One launch for all crops, staged as warp_rois_into stages its operands: the
+// frame and the truncated rects go to HBM once, the kernel writes the crops
+// back to back into scratch, and each crop is copied into its own dst tensor.
+void crop_resize_into(const char* fn, const Tensor& src, std::vector<Tensor>& dst, const std::vector<VRect>& rects,
+                      VSize dsize, int interpolation, const Stats* stats) {
+    if (src.empty()) fail(fn, "empty input tensor");
+    if (src.dtype != INT8 && src.dtype != FP32) fail(fn, "crop_resize takes INT8 or FP32");
+    if (src.layout != NHWC) fail(fn, "the crops of one frame take an NHWC frame");
+    if (interpolation != INTER_LINEAR) fail(fn, "only INTER_LINEAR is supported for the crops of one frame");
+    if (dsize.w < 1 || dsize.h < 1) fail(fn, "dsize must be positive");
+    if (rects.empty()) fail(fn, "empty rect list");
+    const size_t n = rects.size();
+    if (n > 0x7FFFFFFFu) fail(fn, "too many rects");
+    const DType odt = stats ? FP32 : src.dtype;
+    const size_t roi_bytes = (size_t)dsize.w * dsize.h * src.c * dtype_size(odt);
+    detail::Lease lease(detail::compute_device(src));
+    if (src.on_device() && src.device() != lease.device()) fail(fn, "operands live on different devices");
+    const hipStream_t s = lease.stream();
+
+    Tensor rh(4, (int)n, 1, FP32, NCHW);  // the int32 rects, contiguous, in pinned memory (4-byte elements)
+    if (!rh.data) fail(fn, "out of memory staging the rects");
+    int32_t* rp = static_cast<int32_t*>(rh.data);
+    for (size_t i = 0; i < n; ++i) {
+        // crop.cpp:128-131
+        const int left = static_cast<int>(rects[i].left), top = static_cast<int>(rects[i].top);
+        const int cw = static_cast<int>(rects[i].width()), ch = static_cast<int>(rects[i].height());
+        // what crop() and resize() refuse one by one (the kernel would write zeros)
+        if (cw < 2 || ch < 2 || left < 0 || top < 0 || cw > src.w || left > src.w - cw || ch > src.h || top > src.h - ch)
+            fail(fn, "every rect must lie inside the image and hold at least 2 x 2 pixels");
+        rp[4 * i] = left;
+        rp[4 * i + 1] = top;
+        rp[4 * i + 2] = cw;
+        rp[4 * i + 3] = ch;
+    }
+    SyncOnExit guard{s};
+    int32_t* dr = static_cast<int32_t*>(lease.scratch(1, n * 4 * sizeof(int32_t)));
+    detail::check_hip(fn, hipMemcpyAsync(dr, rp, n * 4 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    void* sdev = src.data;
+    if (!src.on_device()) {
+        sdev = lease.scratch(0, src.len());
+        detail::check_hip(fn, hipMemcpyAsync(sdev, src.data, src.len(), hipMemcpyHostToDevice, s));
+    }
+    unsigned char* dout = static_cast<unsigned char*>(lease.scratch(2, n * roi_bytes));
+
+    const vacv_image sd = detail::describe(src, sdev);
+    vacv_image dd{};
+    dd.data = dout;
+    dd.n = (int)n;
+    dd.w = dsize.w;
+    dd.h = dsize.h;
+    dd.c = src.c;
+    dd.dtype = odt;
+    dd.layout = NHWC;
+    if (stats)
+        detail::check(fn, vacv_crop_resize_rois_normalize(&sd, &dd, dr, nullptr, interpolation, VACV_LINEAR_REFERENCE,
+                                                          stats->m(), stats->s(), s));
+    else
+        detail::check(fn, vacv_crop_resize_rois(&sd, &dd, dr, nullptr, interpolation, VACV_LINEAR_REFERENCE, s));
+    dst.resize(n);
+    for (size_t i = 0; i < n; ++i) {
+        dst[i].create_on(src.device(), dsize.w, dsize.h, src.c, odt, NHWC);
+        if (roi_bytes > 0 && !dst[i].data) fail(fn, "out of memory creating the output tensor");
+        detail::check_hip(fn, hipMemcpyAsync(dst[i].data, dout + i * roi_bytes, roi_bytes,
+                                             dst[i].on_device() ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+    }
+    lease.sync(fn);
+}
+
+}  // namespace
+
+void crop_resize(const Tensor& src, std::vector<Tensor>& dst, const std::vector<VRect>& rects, VSize dsize,
+                 int interpolation) {
+    crop_resize_into("va_cv::crop_resize", src, dst, rects, dsize, interpolation, nullptr);
+}
+
+void crop_resize_normalize(const Tensor& src, std::vector<Tensor>& dst, const std::vector<VRect>& rects, VSize dsize,
+                           int interpolation, const Tensor& mean, const Tensor& stddev) {
+    static const char* fn = "va_cv::crop_resize_normalize";
+    const Stats stats = read_stats(fn, mean, stddev, src.c, false);
+    if (!stats.m()) fail(fn, "the crops of one frame need mean and stddev (no per-image statistics)");
+    crop_resize_into(fn, src, dst, rects, dsize, interpolation, &stats);
+}
+
 void cvt_color(const std::vector<Tensor>& src, std::vector<Tensor>& dst, int code) {
     static const char* fn = "va_cv::cvt_color";
     check_batch(fn, src, dst);

@@ -231,6 +231,22 @@ void cvt_color_warp_affine_normalize(const vision::Tensor& yuv, std::vector<visi
                                      const VScalar& borderValue = VScalar(),
                                      const vision::Tensor& mean = vision::Tensor(),
                                      const vision::Tensor& stddev = vision::Tensor());
+/// One frame, rects.size() upright crops, ONE kernel launch: dst[i] =
+/// resize(crop(src, rects[i]), dsize), byte for byte what crop() followed by
+/// resize() gives (taps clamped at the rect's edges; vacv_crop_resize_rois).
+/// src NHWC, INT8 or FP32, c <= 4; INTER_LINEAR only.  The rects are truncated
+/// as crop() truncates them and staged once through the pinned pool with a
+/// host frame; a device frame stays where it is.  A rect that does not lie
+/// inside the frame, or is smaller than 2 x 2, throws.  dst is resized to
+/// rects.size(), each crop with the placement of src.
+void crop_resize(const vision::Tensor& src, std::vector<vision::Tensor>& dst,
+                 const std::vector<vision::VRect>& rects, VSize dsize, int interpolation = INTER_LINEAR);
+/// The same with the fused normalize (FP32 crops); mean and stddev are
+/// required (no per-image statistics for crops).
+void crop_resize_normalize(const vision::Tensor& src, std::vector<vision::Tensor>& dst,
+                           const std::vector<vision::VRect>& rects, VSize dsize, int interpolation = INTER_LINEAR,
+                           const vision::Tensor& mean = vision::Tensor(),
+                           const vision::Tensor& stddev = vision::Tensor());
 void cvt_color(const std::vector<vision::Tensor>& src, std::vector<vision::Tensor>& dst, int code);
 void cvt_color_normalize(const std::vector<vision::Tensor>& src, std::vector<vision::Tensor>& dst, int code,
                          const vision::Tensor& mean = vision::Tensor(),

@@ -12,7 +12,9 @@ from ._lib import (BORDER_CONSTANT, BORDER_REFLECT, BORDER_REFLECT_101, BORDER_R
                    FP16, FP32, FP64, INT8, INTER_AREA, INTER_CUBIC, INTER_LANCZOS4, INTER_LINEAR, INTER_NEAREST, LINEAR_NEON, LINEAR_OPENCV,
                    LINEAR_REFERENCE, NCHW, NHWC, WARP_INVERSE_MAP, VacvError, build)
 
-__all__ = ["ops", "dist", "build", "VacvError", "cvt_color_warp_affine_rois", "cvt_color_warp_affine_rois_normalize"]
+_OPS = ("cvt_color_warp_affine_rois", "cvt_color_warp_affine_rois_normalize", "crop_resize_rois",
+        "crop_resize_rois_normalize", "rects_from_boxes")
+__all__ = ["ops", "dist", "build", "VacvError", *_OPS]
 
 
 def __getattr__(name):
@@ -20,6 +22,6 @@ def __getattr__(name):
     import importlib
     if name in ("ops", "dist"):
         return importlib.import_module(f".{name}", __name__)
-    if name in ("cvt_color_warp_affine_rois", "cvt_color_warp_affine_rois_normalize"):  # ops', on first use
+    if name in _OPS:  # ops', on first use
         return getattr(importlib.import_module(".ops", __name__), name)
     raise AttributeError(name)

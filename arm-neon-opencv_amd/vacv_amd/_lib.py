@@ -91,6 +91,8 @@ SIGNATURES = {
     "vacv_warp_affine_rois": ([_IMG, _IMG, _P, _P, _I, _I, _DP, _P], _I),
     "vacv_warp_affine_rois_normalize": ([_IMG, _IMG, _P, _P, _I, _I, _DP, _FP, _FP, _P], _I),
     "vacv_invert_affine_device": ([_P, _P, _I, _P], _I),
+    "vacv_crop_resize_rois": ([_IMG, _IMG, _P, _P, _I, _I, _P], _I),
+    "vacv_crop_resize_rois_normalize": ([_IMG, _IMG, _P, _P, _I, _I, _FP, _FP, _P], _I),
     "vacv_cvt_color_normalize": ([_IMG, _IMG, _I, _FP, _FP, _P], _I),
     "vacv_cvt_color_resize": ([_IMG, _IMG, _I, _I, _I, _P], _I),
     "vacv_cvt_color_resize_normalize": ([_IMG, _IMG, _I, _I, _I, _FP, _FP, _P], _I),
@@ -115,7 +117,8 @@ TUNE = {"RESIZE_DIRECT": 0, "CUBIC_DIRECT": 1, "RESIZE_INTERLEAVE": 2, "DIRECT_X
 # signature here are laid out for it (tests/test_abi.py checks the header).
 # Bumped with every change to a signature or to the tuning enum (3: round 6,
 # after round 5 added LANCZOS_KERNEL under version 2; 4: the ROI warp entry
-# points and vacv_invert_affine_device; 5: the ROI warp from YUV420sp frames)
+# points and vacv_invert_affine_device; 5: the ROI warp from YUV420sp frames).
+# An added export alone does not bump it (vacv_crop_resize_rois[_normalize]).
 ABI_VERSION = 5
 
 _lib = None

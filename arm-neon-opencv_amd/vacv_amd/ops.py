@@ -334,6 +334,74 @@ def invert_affine_device(ms: torch.Tensor, out=None, stream=None) -> torch.Tenso
     return out
 
 
+def rects_from_boxes(boxes: torch.Tensor) -> torch.Tensor:
+    """(n, 4) float32 boxes (left, top, right, bottom) -> (n, 4) int32 rects
+    (left, top, width, height) as crop_naive truncates them (crop.cpp:128-131):
+    int(left), int(top), int(right - left), int(bottom - top), the differences
+    in float32, every conversion toward zero.  Computed where `boxes` lives, so
+    a detector's device output never visits the host."""
+    if not isinstance(boxes, torch.Tensor) or boxes.dtype != torch.float32:
+        raise ValueError("boxes must be a float32 tensor")
+    if boxes.dim() != 2 or boxes.shape[1] != 4:
+        raise ValueError(f"boxes must have shape (n, 4), got {tuple(boxes.shape)}")
+    lt = boxes[:, :2]
+    return torch.cat([lt, boxes[:, 2:] - lt], 1).to(torch.int32).contiguous()
+
+
+def _crop_rois_args(src: torch.Tensor, rects, src_index):
+    s4 = _as4d(src, NHWC)
+    rects = _device_array(rects, torch.int32, s4.device, "rects")
+    if rects.dim() != 2 or rects.shape[1] != 4:
+        raise ValueError(f"rects must have shape (n, 4), got {tuple(rects.shape)}")
+    n = rects.shape[0]
+    if n < 1:
+        raise ValueError("rects holds no rect")
+    if src_index is not None:
+        src_index = _device_array(src_index, torch.int32, s4.device, "src_index")
+        if tuple(src_index.shape) != (n,):
+            raise ValueError(f"src_index must have shape ({n},), got {tuple(src_index.shape)}")
+    elif s4.shape[0] not in (1, n):
+        raise ValueError(f"without src_index, src must hold 1 or {n} images, not {s4.shape[0]}")
+    return s4, rects, src_index, n
+
+
+def crop_resize_rois(src: torch.Tensor, rects, w: int, h: int, src_index=None, mode: int = LINEAR_REFERENCE,
+                     out=None, stream=None) -> torch.Tensor:
+    """Many upright crops in one launch: out[i] = resize(crop(src[src_index[i]],
+    rects[i]), w, h), the reference's crop + resize chain byte for byte (taps
+    clamped at the rect's edges).  src: NHWC frames (n, h, w, c) or one
+    (h, w, c) / (h, w) frame.  rects: (n, 4) int32 device tensor of (left, top,
+    width, height) (rects_from_boxes makes them from float boxes); src_index:
+    (n,) int32 device tensor, or None (one frame for all, or frame i for ROI i).
+    Both are read by the kernel when it runs on `stream`, not by this call; an
+    invalid rect or index gives a ROI of zeros.  Returns (n, h, w, c)."""
+    s4, rects, src_index, n = _crop_rois_args(src, rects, src_index)
+    if out is None:
+        out = torch.empty((n, h, w, s4.shape[3]), dtype=src.dtype, device=src.device)
+    check("vacv_crop_resize_rois", L.load().vacv_crop_resize_rois(
+        ctypes.byref(describe(s4, NHWC)), ctypes.byref(describe(out, NHWC)), rects.data_ptr(),
+        src_index.data_ptr() if src_index is not None else None, INTER_LINEAR, mode, _stream(stream)))
+    return out
+
+
+def crop_resize_rois_normalize(src: torch.Tensor, rects, w: int, h: int, mean, std, src_index=None,
+                               mode: int = LINEAR_REFERENCE, layout: int = NHWC, out=None,
+                               stream=None) -> torch.Tensor:
+    """crop_resize_rois with the fused normalize: fp32 (n, h, w, c), or planar
+    (n, c, h, w) with layout=NCHW (c = 3 or 1), the model-input layout."""
+    s4, rects, src_index, n = _crop_rois_args(src, rects, src_index)
+    c = s4.shape[3]
+    if mean is None or std is None:
+        raise ValueError("crop_resize_rois_normalize needs mean and stddev (no per-image statistics for ROIs)")
+    if out is None:
+        out = torch.empty((n, h, w, c) if layout == NHWC else (n, c, h, w), dtype=torch.float32, device=src.device)
+    (ma, meanp), (sa, stdp) = _meanstd(mean, std, c)
+    check("vacv_crop_resize_rois_normalize", L.load().vacv_crop_resize_rois_normalize(
+        ctypes.byref(describe(s4, NHWC)), ctypes.byref(describe(out, layout)), rects.data_ptr(),
+        src_index.data_ptr() if src_index is not None else None, INTER_LINEAR, mode, meanp, stdp, _stream(stream)))
+    return out
+
+
 # ---------------------------------------------------------------------------
 # colour
 

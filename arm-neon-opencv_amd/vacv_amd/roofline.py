@@ -170,3 +170,24 @@ def warp_rois_bytes(w_in: int, h_in: int, c: int, w_out: int, h_out: int, ms, in
     for px in _roi_source_pixels(w_in, h_in, w_out, h_out, ms, inverse_map):
         total += px * c * in_esize
     return int(total)
+
+
+def crop_resize_rois_bytes(c: int, in_esize: int, w_out: int, h_out: int, rects, out_esize: int = 1,
+                           w_in: int = None, h_in: int = None) -> int:
+    """B_alg of vacv_crop_resize_rois[_normalize]: the output bytes of every
+    ROI plus each valid rect's w * h * c * in_esize source bytes (a bilinear
+    resize reads every pixel of its crop once, up-scale or down-scale by less
+    than 2; larger down-scales skip rows and columns, which this does not
+    discount).  rects: (n, 4) of (left, top, width, height).  An invalid rect,
+    as the kernel judges it (width or height below 2, a negative origin, or --
+    where the frame size w_in x h_in is given -- an edge past the frame), reads
+    nothing and counts its output only."""
+    r = np.asarray(rects, dtype=np.int64).reshape(-1, 4)
+    total = r.shape[0] * w_out * h_out * c * out_esize
+    for left, top, w, h in r.tolist():
+        if w < 2 or h < 2 or left < 0 or top < 0:
+            continue
+        if (w_in is not None and left + w > w_in) or (h_in is not None and top + h > h_in):
+            continue
+        total += w * h * c * in_esize
+    return int(total)

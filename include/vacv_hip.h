@@ -32,6 +32,9 @@
 extern "C" {
 #endif
 
+/* Bumped when a signature, an enum value or the tuning enum changes.  An
+ * added export alone does not bump it (vacv_crop_resize_rois[_normalize] came
+ * under 5): a caller built against the older header still gets what it asked. */
 #define VACV_ABI_VERSION 5
 #define VACV_MAX_CHANNELS 16
 
@@ -314,6 +317,53 @@ int vacv_warp_affine_rois_normalize(const vacv_image* src, const vacv_image* dst
 /* inv[i] = vacv_invert_affine(m[i]) for n maps, bit for bit.  DEVICE in,
  * DEVICE out, queued on `stream`. */
 int vacv_invert_affine_device(const float* m, float* inv, int n, void* stream);
+
+/* Many upright crops in one launch: the reference's crop(src, box) followed
+ * by resize(crop, dsize) per detected box (Crop::crop_naive, crop.cpp:128-142,
+ * then ResizeNaive::resize_naive_inter_linear_u8 / _fp32), without the crops
+ * in between.  Not a scale-and-translate vacv_warp_affine_rois: the resize has
+ * half-pixel centres, 11-bit weights and taps clamped at the crop's edge.
+ * dst image i = rect rects[i] of src image src_index[i], resized to
+ * dst->w x dst->h.
+ * src: `src->n` frames, NHWC, c = 1..4, INT8 or FP32, pitched or dense, any
+ *      base alignment (NCHW: UNSUPPORTED; smaller than 2 x 2: INVALID_ARG).
+ * dst: `dst->n` = number of ROIs, all dst->w x dst->h, dtype and layout of
+ *      src; ROIs may be pitched (row and batch pitch).
+ * rects:     DEVICE array [dst->n][4] int32 {left, top, width, height},
+ *            already truncated as crop_naive truncates a box (crop.cpp:128-131).
+ *            NULL: INVALID_ARG.
+ * src_index: DEVICE array [dst->n] int32, or NULL, with the NULL rules of
+ *            vacv_warp_affine_rois.
+ * Both arrays are read by the kernel, on `stream`, at execution time: the
+ * call copies nothing between host and device, allocates nothing and never
+ * synchronizes, and host code never dereferences them.
+ * interpolation: INTER_LINEAR (else UNSUPPORTED).  mode: VACV_LINEAR_* as in
+ * vacv_resize (a value outside them: INVALID_ARG); it selects the INT8
+ * arithmetic and has no effect on FP32.
+ * ROI i is byte-identical to vacv_crop(frame src_index[i], rect i) followed by
+ * vacv_resize(..., INTER_LINEAR, mode) to dst->w x dst->h: the taps clamp at
+ * the RECT's edges, never the frame's, and a rect of the output's size is the
+ * plain crop.  Bytes of the dst allocation outside the ROI rectangles are
+ * never written.
+ * Device-supplied values cannot fault: a rect with width < 2, height < 2,
+ * left < 0, top < 0, left + width > src->w or top + height > src->h (the sums
+ * taken without int overflow), or a src_index[i] outside [0, src->n), gives a
+ * ROI of zeros and reads no source byte; every other read is range-checked
+ * against the indexed frame by the hardware.
+ * A destination wider than 2^20 pixels or a frame of 2 GiB or more:
+ * UNSUPPORTED. */
+int vacv_crop_resize_rois(const vacv_image* src, const vacv_image* dst, const int32_t* rects,
+                          const int32_t* src_index, int interpolation, int mode, void* stream);
+/* The same, normalized: dst is FP32, NHWC or NCHW (planar output for c = 3
+ * and c = 1; other channel counts: UNSUPPORTED), pitched or dense (row, plane
+ * and batch pitch).  mean / stddev: host arrays of c floats, both required
+ * (one NULL: INVALID_ARG; both NULL, per-image statistics: UNSUPPORTED).
+ * ROI i is byte-identical to vacv_crop and vacv_resize_normalize on that
+ * rect, followed by vacv_change_layout when dst is NCHW; an invalid rect or
+ * index gives the normalized value of 0 in every channel. */
+int vacv_crop_resize_rois_normalize(const vacv_image* src, const vacv_image* dst, const int32_t* rects,
+                                    const int32_t* src_index, int interpolation, int mode,
+                                    const float* mean, const float* stddev, void* stream);
 
 /* cvt_color then normalize (the cfg3 pipeline), dst (w,h,3) FP32 NHWC. */
 int vacv_cvt_color_normalize(const vacv_image* src, const vacv_image* dst, int code,

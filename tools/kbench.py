@@ -28,7 +28,8 @@ def main():
     ap.add_argument("--compare", action="store_true",
                     help="--op warp_rois: time each one-call case against the same crops as a loop of single "
                          "calls (vacv_warp_affine; vacv_warp_affine_normalize + one vacv_change_layout), alternating; "
-                         "--op yuv_rois: against vacv_cvt_color of all frames + vacv_warp_affine_rois[_normalize]")
+                         "--op yuv_rois: against vacv_cvt_color of all frames + vacv_warp_affine_rois[_normalize]; "
+                         "--op crop_resize_rois: against a loop of vacv_crop + vacv_resize[_normalize] single calls")
     ap.add_argument("--baseline-lib", default="",
                     help="--compare: libvacv_hip.so of another build (e.g. the parent commit's) to run the loop on; "
                          "default: this build's own single-call entry points")
@@ -268,8 +269,53 @@ def main():
             lambda yuv7=yuv7, dms7=dms7, o7=o7: ops.cvt_color_warp_affine_rois(yuv7, dms7, 140, 210, out=o7),
             yuv_warp_rois_bytes(1280, 720, 140, 210, ms7), 64 * 140 * 210)
         chains["yuv_rois_720p_64x140x210_u8"] = dict(yuv=yuv7, ms=dms7, idx=None, out=torch.empty_like(o7), norm=False)
+    crop_loops = {}
+    if a.op in ("crop_resize_rois", "all"):
+        # many upright crops, each with its own rect, in ONE launch
+        # (vacv_crop_resize_rois): seeded boxes of 32..400 pixels per side
+        # anywhere inside the frame, mirroring the warp_rois cases
+        import numpy as np
+        from vacv_amd.roofline import crop_resize_rois_bytes
+        rng = np.random.default_rng(20261020)
+
+        def roi_rects(n, fw, fh, lo=32, hi=400):
+            wh = rng.integers(lo, hi + 1, (n, 2))
+            lt = (rng.random((n, 2)) * (np.array([fw, fh]) - wh + 1)).astype(np.int64)
+            return np.concatenate([lt, wh], 1).astype(np.int32)
+
+        src = frames(8, 1080, 1920)
+        rects = roi_rects(256, 1920, 1080)
+        idx = np.arange(256, dtype=np.int32) % 8
+        drects, didx = torch.from_numpy(rects).to(dev), torch.from_numpy(idx).to(dev)
+        o = torch.empty((256, 112, 112, 3), dtype=torch.uint8, device=dev)
+        cases["crop_resize_rois_1080p_256x112_u8"] = (
+            lambda src=src, drects=drects, didx=didx, o=o: ops.crop_resize_rois(src, drects, 112, 112, src_index=didx,
+                                                                               out=o),
+            crop_resize_rois_bytes(3, 1, 112, 112, rects, 1), 256 * 112 * 112)
+        crop_loops["crop_resize_rois_1080p_256x112_u8"] = dict(src=src, rects=rects, idx=idx, out=torch.empty_like(o),
+                                                               norm=False)
+        of = torch.empty((256, 3, 112, 112), dtype=torch.float32, device=dev)
+        cases["crop_resize_rois_normalize_1080p_256x112_chw"] = (
+            lambda src=src, drects=drects, didx=didx, of=of: ops.crop_resize_rois_normalize(
+                src, drects, 112, 112, MEAN, STD, src_index=didx, layout=vacv_amd.NCHW, out=of),
+            crop_resize_rois_bytes(3, 1, 112, 112, rects, 4), 256 * 112 * 112)
+        crop_loops["crop_resize_rois_normalize_1080p_256x112_chw"] = dict(src=src, rects=rects, idx=idx,
+                                                                          out=torch.empty_like(of), norm=True)
+        # the reference harness's crop size: 64 crops of one 1280 x 720 frame
+        src7 = frames(1, 720, 1280)
+        rects7 = roi_rects(64, 1280, 720)
+        drects7 = torch.from_numpy(rects7).to(dev)
+        o7 = torch.empty((64, 210, 140, 3), dtype=torch.uint8, device=dev)
+        cases["crop_resize_rois_720p_64x140x210_u8"] = (
+            lambda src7=src7, drects7=drects7, o7=o7: ops.crop_resize_rois(src7, drects7, 140, 210, out=o7),
+            crop_resize_rois_bytes(3, 1, 140, 210, rects7, 1), 64 * 140 * 210)
+        crop_loops["crop_resize_rois_720p_64x140x210_u8"] = dict(src=src7, rects=rects7, idx=np.zeros(64, np.int32),
+                                                                 out=torch.empty_like(o7), norm=False)
     if a.only:
         cases = {k: v for k, v in cases.items() if a.only in k}
+    if a.compare and a.op == "crop_resize_rois":
+        compare_with_crop_loops({k: v for k, v in cases.items() if k in crop_loops}, crop_loops, a.iters)
+        return
     if a.compare and a.op == "yuv_rois":
         compare_with_chains({k: v for k, v in cases.items() if k in chains}, chains, a.baseline_lib, a.iters)
         return
@@ -441,6 +487,102 @@ def compare_with_chains(cases, chains, baseline_lib, iters):
                           "chain_over_one_call": round(mc / mo, 2), "alg_bytes": int(nbytes),
                           "one_call_alg_GBps": round(nbytes / mo / 1e6, 1), "outputs_equal": same,
                           "clock": "host, stream synchronised"}), flush=True)
+
+
+def compare_with_crop_loops(cases, loops, iters):
+    """--op crop_resize_rois: the one call against the same crops as a loop of
+    vacv_crop + vacv_resize (or vacv_resize_normalize, then one
+    vacv_change_layout) single calls on this build, per case: both timed end to
+    end with a host clock around a synchronised stream, alternating, after
+    warm-up; outputs compared equal.  The loop's descriptors, crop buffers and
+    ctypes references are built beforehand, so what is timed is the library.
+    Also per case the one call's time between device events (the kernel), and
+    for the 112 x 112 cases that of vacv_warp_affine_rois[_normalize] on the
+    scale-and-translate maps of the same boxes (the neighbouring kernel doing
+    comparable work, other arithmetic: for orientation only)."""
+    import ctypes
+    import time
+
+    import numpy as np
+    import torch
+    import vacv_amd
+    from vacv_amd import _lib as L, ops
+    lib = L.load()
+    stream = ops._stream()
+    mean, std = (ctypes.c_float * 3)(*MEAN), (ctypes.c_float * 3)(*STD)
+
+    def events_ms(f):
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)]
+        s = torch.cuda.current_stream()
+        for e0, e1 in ev:
+            e0.record(s)
+            f()
+            e1.record(s)
+        torch.cuda.synchronize()
+        return sorted(e0.elapsed_time(e1) for e0, e1 in ev)[iters // 2]
+
+    for name, (fn, nbytes, px) in cases.items():
+        lp = loops[name]
+        src, rects, idx, out, norm = lp["src"], lp["rects"], lp["idx"], lp["out"], lp["norm"]
+        n = len(rects)
+        ho, wo = (out.shape[2], out.shape[3]) if norm else (out.shape[1], out.shape[2])
+        tmp = torch.empty((n, ho, wo, 3), dtype=torch.float32, device=out.device) if norm else out
+        crops = [torch.empty((1, int(h), int(w), 3), dtype=torch.uint8, device=out.device) for _, _, w, h in rects]
+        keep = ([ops.describe(src[i:i + 1]) for i in range(src.shape[0])], [ops.describe(c) for c in crops],
+                [ops.describe(tmp[i:i + 1]) for i in range(n)])
+        fd, cd, dd = ([ctypes.byref(d) for d in ds] for ds in keep)
+        whole_tmp, whole_out = ops.describe(tmp), ops.describe(out, vacv_amd.NCHW if norm else vacv_amd.NHWC)
+        frame_of = [int(k) for k in idx]
+        lt = [(int(r[0]), int(r[1])) for r in rects]
+
+        def loop():
+            for i in range(n):
+                assert lib.vacv_crop(fd[frame_of[i]], cd[i], lt[i][0], lt[i][1], stream) == 0
+                if norm:
+                    assert lib.vacv_resize_normalize(cd[i], dd[i], 1, 0, mean, std, stream) == 0
+                else:
+                    assert lib.vacv_resize(cd[i], dd[i], 1, 0, stream) == 0
+            if norm:
+                assert lib.vacv_change_layout(ctypes.byref(whole_tmp), ctypes.byref(whole_out), stream) == 0
+
+        def timed(f):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            f()
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) * 1e3
+
+        for _ in range(5):
+            loop()
+            one = fn()
+        torch.cuda.synchronize()
+        same = bool(torch.equal(one, out))  # both legs compute the same crops
+        t_loop, t_one = [], []
+        for _ in range(iters):
+            t_loop.append(timed(loop))
+            t_one.append(timed(fn))
+        ml, mo = sorted(t_loop)[iters // 2], sorted(t_one)[iters // 2]
+        line = {"case": name, "rois": n, "frames": int(src.shape[0]), "baseline": "this build",
+                "loop_ms_median": round(ml, 4), "loop_ms_min": round(min(t_loop), 4),
+                "one_call_ms_median": round(mo, 4), "one_call_ms_min": round(min(t_one), 4),
+                "loop_over_one_call": round(ml / mo, 2), "kernel_ms_median": round(events_ms(fn), 4),
+                "alg_bytes": int(nbytes), "outputs_equal": same, "clock": "host, stream synchronised; kernel: events"}
+        if (wo, ho) == (112, 112):
+            # dst = s * src + t with the box onto the whole output
+            sx, sy = wo / rects[:, 2].astype(np.float64), ho / rects[:, 3].astype(np.float64)
+            ms = np.stack([sx, 0 * sx, -sx * rects[:, 0], 0 * sy, sy, -sy * rects[:, 1]], 1).astype(np.float32)
+            dms, didx = torch.from_numpy(ms).to(out.device), torch.from_numpy(np.asarray(idx, np.int32)).to(out.device)
+            wout = torch.empty_like(out)
+            if norm:
+                warp = lambda: ops.warp_affine_rois_normalize(src, dms, wo, ho, MEAN, STD, src_index=didx,
+                                                              out_layout=vacv_amd.NCHW, out=wout)
+            else:
+                warp = lambda: ops.warp_affine_rois(src, dms, wo, ho, src_index=didx, out=wout)
+            for _ in range(5):
+                warp()
+            torch.cuda.synchronize()
+            line["warp_rois_same_boxes_kernel_ms_median"] = round(events_ms(warp), 4)
+        print(json.dumps(line), flush=True)
 
 
 def run_cases(cases, iters, tag):
