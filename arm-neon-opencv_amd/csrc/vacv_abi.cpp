@@ -13,10 +13,8 @@
 #include <cfloat>
 #include <cmath>
 #include <cstdint>
-#include <cstdlib>
 #include <cstring>
 #include <map>
-#include <set>
 #include <mutex>
 #include <tuple>
 #include <utility>
@@ -282,6 +280,8 @@ int resize_impl(const vacv_image* src_d, const vacv_image* dst_d, int interpolat
     L.mode = mode;
     L.out = out_kind;
     if (ns) L.norm = *ns;
+    // inv_scale as cv::resize computes it (AREA, LANCZOS4)
+    const double ifx = fx > 0 ? fx : (double)dst.w / src.w, ify = fy > 0 ? fy : (double)dst.h / src.h;
     if (interpolation == VACV_INTER_LINEAR) {
         if (src.w < 2 || src.h < 2) return VACV_ERR_INVALID_ARG;  // resize_naive.cpp:28-31 needs 2 taps
         if (src.dtype == VACV_INT8) {
@@ -317,7 +317,6 @@ int resize_impl(const vacv_image* src_d, const vacv_image* dst_d, int interpolat
         // its bilinear resize with area-mode taps for up-scales (k_area.hip)
         if (src.dtype != VACV_INT8 && src.dtype != VACV_FP32) return VACV_ERR_UNSUPPORTED;
         if ((st = resolve_out(src, dst, out_kind, L.out))) return st;
-        const double ifx = fx > 0 ? fx : (double)dst.w / src.w, ify = fy > 0 ? fy : (double)dst.h / src.h;
         const double sx = 1. / ifx, sy = 1. / ify;
         const double ix = std::nearbyint(sx), iy = std::nearbyint(sy);
         if (sx >= 1 && sy >= 1 && std::fabs(sx - ix) < DBL_EPSILON && std::fabs(sy - iy) < DBL_EPSILON) {
@@ -339,7 +338,6 @@ int resize_impl(const vacv_image* src_d, const vacv_image* dst_d, int interpolat
         // (k_lanczos.hip), u8 in fixed point, fp32 in float
         if (src.dtype != VACV_INT8 && src.dtype != VACV_FP32) return VACV_ERR_UNSUPPORTED;
         if ((st = resolve_out(src, dst, out_kind, L.out))) return st;
-        const double ifx = fx > 0 ? fx : (double)dst.w / src.w, ify = fy > 0 ? fy : (double)dst.h / src.h;
         return launch_resize_lanczos(L, ifx, ify, s);
     } else {
         return VACV_ERR_UNSUPPORTED;  // resize.cpp:46-49 recurses forever for other modes
@@ -491,6 +489,77 @@ int rois_options(int flags, int border_mode) {
     return VACV_OK;
 }
 
+// ---- what the batched ROI entry points share ---------------------------------
+// Each impl below calls these where its own order of checks has them: which
+// check fails first is behaviour (tests/test_rois_status_grid.py).
+
+// src_index null: one frame for every ROI, or frame i for ROI i
+bool roi_frames_ok(const Img& src, const Img& dst, const int32_t* src_index) {
+    return src_index || src.n == 1 || src.n == dst.n;
+}
+
+// What the bilinear ROI kernels sample: INT8 or FP32, NHWC, at most 4 channels
+int roi_source(const Img& src) {
+    if (src.dtype != VACV_INT8 && src.dtype != VACV_FP32) return VACV_ERR_UNSUPPORTED;
+    if (src.layout != VACV_NHWC) return VACV_ERR_UNSUPPORTED;
+    return src.c > 4 ? VACV_ERR_UNSUPPORTED : VACV_OK;
+}
+
+// ... with two taps each way (resize_naive.cpp:28-31)
+bool two_taps(const Img& src) { return src.w >= 2 && src.h >= 2; }
+
+// dst is FP32 with statistics, else `same` and NHWC.  planar: the NCHW output
+// of 3 channels; one channel is the same bytes either way
+int roi_output(const Img& dst, int same, const NormSpec* ns, bool& planar) {
+    if (dst.dtype != (ns ? VACV_FP32 : same)) return VACV_ERR_INVALID_ARG;
+    if (!ns && dst.layout != VACV_NHWC) return VACV_ERR_INVALID_ARG;
+    planar = dst.layout == VACV_NCHW && dst.c > 1;
+    return planar && dst.c != 3 ? VACV_ERR_UNSUPPORTED : VACV_OK;
+}
+
+// the fields every ROI launch has
+template <class Launch>
+void roi_fill(Launch& L, const Img& src, const Img& dst, const int32_t* src_index, bool planar, const NormSpec* ns) {
+    L.dst = geom(dst);
+    L.n_src = src.n;
+    L.n_roi = dst.n;
+    L.src_index = src_index;
+    L.out = ns ? kOutNorm : kOutSame;
+    L.planar = planar;
+    if (ns) L.norm = *ns;
+}
+
+// ... and the sampler's of the two warps
+template <class Launch>
+void roi_fill_warp(Launch& L, const Img& src, const float* m, int flags, int border_mode, const double bv[4]) {
+    L.m = m;
+    L.inverse_map = (flags & VACV_WARP_INVERSE_MAP) != 0;
+    border_values(src, bv, L.border);
+    L.border_mode = border_mode;
+}
+
+// The _rois_normalize entry points' statistics: both given (per-image
+// statistics of a ROI are not built), before the descriptors are looked at;
+// one value per channel of dst, the source's channels (`decoded`: the 3 of the
+// decoded frame).
+int roi_norm_spec(const vacv_image* src_d, const vacv_image* dst_d, const float* mean, const float* stddev,
+                  bool decoded, NormSpec& ns) {
+    if (!mean && !stddev) return VACV_ERR_UNSUPPORTED;
+    if (!mean || !stddev) return VACV_ERR_INVALID_ARG;
+    Img src, dst;
+    const int st = load2(src_d, dst_d, src, dst);
+    if (st) return st;
+    if (dst.c != (decoded ? 3 : src.c)) return VACV_ERR_INVALID_ARG;
+    return norm_spec(dst, mean, stddev, ns);
+}
+
+// The decoded height of a YUV420sp frame (h rows of Y, h / 2 of chroma;
+// cvt_color.cpp:152), or INVALID_ARG for a shape that is none
+int yuv420sp_height(const Img& src) {
+    const int h = src.h / 3 * 2;
+    return src.w % 2 || h % 2 || h < 2 || src.h != h / 2 * 3 ? VACV_ERR_INVALID_ARG : h;
+}
+
 // vacv_warp_affine_rois[_normalize]: dst image i = warp of src image
 // src_index[i] under m[i].  m and src_index are device arrays: validated for
 // presence only, never read here.  ns: host-constant statistics (fp32 output,
@@ -502,31 +571,17 @@ int warp_rois_impl(const vacv_image* src_d, const vacv_image* dst_d, const float
     if (st) return st;
     if (!m) return VACV_ERR_INVALID_ARG;
     if (src.c != dst.c) return VACV_ERR_INVALID_ARG;
-    if (!src_index && src.n != 1 && src.n != dst.n) return VACV_ERR_INVALID_ARG;
-    if (src.dtype != VACV_INT8 && src.dtype != VACV_FP32) return VACV_ERR_UNSUPPORTED;
-    if (src.layout != VACV_NHWC) return VACV_ERR_UNSUPPORTED;
+    if (!roi_frames_ok(src, dst, src_index)) return VACV_ERR_INVALID_ARG;
+    if ((st = roi_source(src))) return st;
     if ((st = rois_options(flags, border_mode))) return st;
-    if (src.c > 4) return VACV_ERR_UNSUPPORTED;
-    if (src.w < 2 || src.h < 2) return VACV_ERR_INVALID_ARG;
-    if (dst.dtype != (ns ? VACV_FP32 : src.dtype)) return VACV_ERR_INVALID_ARG;
-    if (!ns && dst.layout != VACV_NHWC) return VACV_ERR_INVALID_ARG;  // dst layout = src's
-    // planar output: 3 channels; one channel is the same bytes either way
-    const bool planar = dst.layout == VACV_NCHW && dst.c > 1;
-    if (planar && dst.c != 3) return VACV_ERR_UNSUPPORTED;
+    if (!two_taps(src)) return VACV_ERR_INVALID_ARG;
+    bool planar;
+    if ((st = roi_output(dst, src.dtype, ns, planar))) return st;
     WarpRoisLaunch L{};
     L.src = geom(src);
     if (L.src.plane_bytes > kMaxPlaneBytes) return VACV_ERR_UNSUPPORTED;
-    L.dst = geom(dst);
-    L.n_src = src.n;
-    L.n_roi = dst.n;
-    L.m = m;
-    L.src_index = src_index;
-    L.inverse_map = (flags & VACV_WARP_INVERSE_MAP) != 0;
-    border_values(src, bv, L.border);
-    L.border_mode = border_mode;
-    L.out = ns ? kOutNorm : kOutSame;
-    L.planar = planar;
-    if (ns) L.norm = *ns;
+    roi_fill(L, src, dst, src_index, planar, ns);
+    roi_fill_warp(L, src, m, flags, border_mode, bv);
     return hip_status(launch_warp_rois(L, s));
 }
 
@@ -540,29 +595,18 @@ int crop_resize_rois_impl(const vacv_image* src_d, const vacv_image* dst_d, cons
     if (st) return st;
     if (!rects) return VACV_ERR_INVALID_ARG;
     if (src.c != dst.c) return VACV_ERR_INVALID_ARG;
-    if (!src_index && src.n != 1 && src.n != dst.n) return VACV_ERR_INVALID_ARG;
-    if (src.dtype != VACV_INT8 && src.dtype != VACV_FP32) return VACV_ERR_UNSUPPORTED;
-    if (src.layout != VACV_NHWC) return VACV_ERR_UNSUPPORTED;
+    if (!roi_frames_ok(src, dst, src_index)) return VACV_ERR_INVALID_ARG;
+    if ((st = roi_source(src))) return st;
     if (interpolation != VACV_INTER_LINEAR) return VACV_ERR_UNSUPPORTED;
-    if (src.c > 4) return VACV_ERR_UNSUPPORTED;
     if (mode < VACV_LINEAR_REFERENCE || mode > VACV_LINEAR_OPENCV) return VACV_ERR_INVALID_ARG;
-    if (src.w < 2 || src.h < 2) return VACV_ERR_INVALID_ARG;  // resize_naive.cpp:28-31 needs 2 taps
-    if (dst.dtype != (ns ? VACV_FP32 : src.dtype)) return VACV_ERR_INVALID_ARG;
-    if (!ns && dst.layout != VACV_NHWC) return VACV_ERR_INVALID_ARG;  // dst layout = src's
-    // planar output: 3 channels; one channel is the same bytes either way
-    const bool planar = dst.layout == VACV_NCHW && dst.c > 1;
-    if (planar && dst.c != 3) return VACV_ERR_UNSUPPORTED;
+    if (!two_taps(src)) return VACV_ERR_INVALID_ARG;
+    bool planar;
+    if ((st = roi_output(dst, src.dtype, ns, planar))) return st;
     CropResizeRoisLaunch L{};
     L.src = geom(src);
-    L.dst = geom(dst);
-    L.n_src = src.n;
-    L.n_roi = dst.n;
+    roi_fill(L, src, dst, src_index, planar, ns);
     L.rects = rects;
-    L.src_index = src_index;
     L.mode = mode;
-    L.out = ns ? kOutNorm : kOutSame;
-    L.planar = planar;
-    if (ns) L.norm = *ns;
     if (!crop_resize_rois_fits(L)) return VACV_ERR_UNSUPPORTED;
     return hip_status(launch_crop_resize_rois(L, s));
 }
@@ -585,8 +629,8 @@ int color_impl(const vacv_image* src_d, const vacv_image* dst_d, int code, int o
     int v_first, rgb;
     if ((st = color_code(code, v_first, rgb))) return st;
     if (src.dtype != VACV_INT8 || src.c != 1) return VACV_ERR_INVALID_ARG;
-    const int h = src.h / 3 * 2;  // cvt_color.cpp:152
-    if (src.w % 2 || h % 2 || h < 2 || src.h != h / 2 * 3) return VACV_ERR_INVALID_ARG;
+    const int h = yuv420sp_height(src);
+    if (h < 0) return h;
     if (dst.w != src.w || dst.h != h || dst.c != 3 || dst.layout != VACV_NHWC || dst.n != src.n)
         return VACV_ERR_INVALID_ARG;
     const int want = out_kind == kOutSame ? VACV_INT8 : VACV_FP32;
@@ -637,8 +681,8 @@ int color_cv_impl(const vacv_image* src_d, const vacv_image* dst_d, int code, hi
         return hip_status(launch_color_cv(L, s));
     }
     if (src.dtype != VACV_INT8 || dst.dtype != VACV_INT8) return VACV_ERR_INVALID_ARG;
-    const int h = src.h / 3 * 2;  // cvt_color.cpp:152, as cv::cvtColor's YUV420 sizes
-    if (src.w % 2 || h % 2 || h < 2 || src.h != h / 2 * 3) return VACV_ERR_INVALID_ARG;
+    const int h = yuv420sp_height(src);  // as cv::cvtColor's YUV420 sizes
+    if (h < 0) return h;
     L.h = h;
     switch (code) {
         case VACV_COLOR_YUV2RGBA_NV12: L.layout = 0; L.dcn = 4; L.bidx = 2; break;
@@ -667,9 +711,9 @@ int yuv_resize_impl(const vacv_image* src_d, const vacv_image* dst_d, int code, 
     if (interpolation != VACV_INTER_LINEAR) return VACV_ERR_UNSUPPORTED;
     if (mode < VACV_LINEAR_REFERENCE || mode > VACV_LINEAR_OPENCV) return VACV_ERR_INVALID_ARG;
     if (src.dtype != VACV_INT8 || src.c != 1 || src.layout != VACV_NHWC) return VACV_ERR_INVALID_ARG;
-    const int h = src.h / 3 * 2;  // cvt_color.cpp:152
+    const int h = yuv420sp_height(src);
     // w >= 4: the chroma gather reads 4 bytes within the row
-    if (src.w % 2 || h % 2 || h < 2 || src.w < 4 || src.h != h / 2 * 3) return VACV_ERR_INVALID_ARG;
+    if (h < 0 || src.w < 4) return VACV_ERR_INVALID_ARG;
     if (dst.c != 3 || dst.n != src.n) return VACV_ERR_INVALID_ARG;
     const int want = out_kind == kOutSame ? VACV_INT8 : VACV_FP32;
     if (dst.dtype != want) return VACV_ERR_INVALID_ARG;
@@ -718,99 +762,50 @@ int yuv_rois_impl(const vacv_image* src_d, const vacv_image* dst_d, int code, co
     int v_first, rgb;
     if ((st = color_code(code, v_first, rgb))) return st;
     if (src.dtype != VACV_INT8 || src.c != 1 || src.layout != VACV_NHWC) return VACV_ERR_INVALID_ARG;
-    const int h = src.h / 3 * 2;  // cvt_color.cpp:152
-    if (src.w % 2 || h % 2 || h < 2 || src.h != h / 2 * 3) return VACV_ERR_INVALID_ARG;
+    const int h = yuv420sp_height(src);
+    if (h < 0) return h;
     if (dst.c != 3) return VACV_ERR_INVALID_ARG;
-    if (!src_index && src.n != 1 && src.n != dst.n) return VACV_ERR_INVALID_ARG;
+    if (!roi_frames_ok(src, dst, src_index)) return VACV_ERR_INVALID_ARG;
     if ((st = rois_options(flags, border_mode))) return st;
-    if (dst.dtype != (ns ? VACV_FP32 : VACV_INT8)) return VACV_ERR_INVALID_ARG;
-    if (!ns && dst.layout != VACV_NHWC) return VACV_ERR_INVALID_ARG;  // decoded frames are NHWC
+    bool planar;  // decoded frames are u8 NHWC
+    if ((st = roi_output(dst, VACV_INT8, ns, planar))) return st;
     YuvRoisLaunch L{};
     L.src = src.data;
     L.src_img = src.batch;
     L.src_row = src.row;
     L.src_bytes = src.row * (src.h - 1) + src.w;
     if (L.src_bytes > kMaxPlaneBytes) return VACV_ERR_UNSUPPORTED;
-    L.dst = geom(dst);
-    L.n_src = src.n;
-    L.n_roi = dst.n;
+    roi_fill(L, src, dst, src_index, planar, ns);
+    roi_fill_warp(L, src, m, flags, border_mode, bv);
     L.w = src.w;
     L.h = h;
-    L.m = m;
-    L.src_index = src_index;
-    L.inverse_map = (flags & VACV_WARP_INVERSE_MAP) != 0;
-    border_values(src, bv, L.border);
-    L.border_mode = border_mode;
     L.v_first = v_first;
     L.rgb = rgb;
-    L.out = ns ? kOutNorm : kOutSame;
-    L.planar = dst.layout == VACV_NCHW;
-    if (ns) L.norm = *ns;
     return hip_status(launch_yuv_rois(L, s));
 }
 
-// Shape of the fp32 output viewed as its own image (for the auto-stats passes).
-int fused_normalize(const vacv_image* dst_d, const float* mean, const float* stddev, hipStream_t s,
-                    int (*pass)(const void*, int, const NormSpec*, hipStream_t), const void* ctx) {
+// An operator with the fused normalize.  pass(out_kind, ns) queues the operator
+// writing dst: normalized with the given statistics, or (no statistics: those
+// of its own fp32 output, per image) raw fp32, normalized in place afterwards.
+template <class Pass>
+int fused_normalize(const vacv_image* dst_d, const float* mean, const float* stddev, hipStream_t s, Pass pass) {
     Img dst;
     int st = load(dst_d, dst);
     if (st) return st;
     if (dst.dtype != VACV_FP32) return VACV_ERR_INVALID_ARG;
     NormSpec ns;
     if ((st = norm_spec(dst, mean, stddev, ns))) return st;
-    if (ns.mode == 1) return pass(ctx, kOutNorm, &ns, s);
+    if (ns.mode == 1) return pass(kOutNorm, &ns);
     // auto statistics: raw fp32 result, per-image stats of it, normalize in place.
     // What per_image_stats refuses is refused here, before the first pass writes dst.
     if ((dst.layout == VACV_NHWC && dst.c > 4) || !dense(dst)) return VACV_ERR_UNSUPPORTED;
-    if ((st = pass(ctx, kOutF32, nullptr, s))) return st;
+    if ((st = pass(kOutF32, nullptr))) return st;
     float *dm = nullptr, *ds = nullptr;
     if ((st = per_image_stats(dst, s, &dm, &ds))) return st;
     ns.mode = 2;
     ns.dev_mean = dm;
     ns.dev_std = ds;
     return normalize_with(dst, dst, ns, s);
-}
-
-struct ResizeCtx {
-    const vacv_image* src;
-    const vacv_image* dst;
-    int interpolation, mode;
-};
-int resize_pass(const void* c, int out, const NormSpec* ns, hipStream_t s) {
-    const ResizeCtx* r = static_cast<const ResizeCtx*>(c);
-    return resize_impl(r->src, r->dst, r->interpolation, r->mode, out, ns, s);
-}
-
-struct WarpCtx {
-    const vacv_image* src;
-    const vacv_image* dst;
-    const float* m;
-    int flags, border;
-    const double* bv;
-};
-int warp_pass(const void* c, int out, const NormSpec* ns, hipStream_t s) {
-    const WarpCtx* w = static_cast<const WarpCtx*>(c);
-    return warp_impl(w->src, w->dst, w->m, w->flags, w->border, w->bv, out, ns, s);
-}
-
-struct ColorCtx {
-    const vacv_image* src;
-    const vacv_image* dst;
-    int code;
-};
-int color_pass(const void* c, int out, const NormSpec* ns, hipStream_t s) {
-    const ColorCtx* k = static_cast<const ColorCtx*>(c);
-    return color_impl(k->src, k->dst, k->code, out, ns, s);
-}
-
-struct YuvResizeCtx {
-    const vacv_image* src;
-    const vacv_image* dst;
-    int code, interpolation, mode;
-};
-int yuv_resize_pass(const void* c, int out, const NormSpec* ns, hipStream_t s) {
-    const YuvResizeCtx* k = static_cast<const YuvResizeCtx*>(c);
-    return yuv_resize_impl(k->src, k->dst, k->code, k->interpolation, k->mode, out, ns, s);
 }
 
 }  // namespace
@@ -970,15 +965,9 @@ int vacv_warp_affine_rois_normalize(const vacv_image* src, const vacv_image* dst
                                     const int32_t* src_index, int flags, int border_mode,
                                     const double border_value[4], const float* mean, const float* stddev,
                                     void* stream) {
-    if (!mean && !stddev) return VACV_ERR_UNSUPPORTED;  // per-image statistics of a ROI: not built
-    if (!mean || !stddev) return VACV_ERR_INVALID_ARG;
-    Img sm, d;
-    int st = load(src, sm);
-    if (st) return st;
-    if ((st = load(dst, d))) return st;
-    if (sm.c != d.c) return VACV_ERR_INVALID_ARG;  // mean / stddev hold the source's c values
     NormSpec ns;
-    if ((st = norm_spec(d, mean, stddev, ns))) return st;
+    const int st = roi_norm_spec(src, dst, mean, stddev, false, ns);
+    if (st) return st;
     return warp_rois_impl(src, dst, m, src_index, flags, border_mode, border_value, &ns, (hipStream_t)stream);
 }
 
@@ -990,15 +979,9 @@ int vacv_crop_resize_rois(const vacv_image* src, const vacv_image* dst, const in
 int vacv_crop_resize_rois_normalize(const vacv_image* src, const vacv_image* dst, const int32_t* rects,
                                     const int32_t* src_index, int interpolation, int mode, const float* mean,
                                     const float* stddev, void* stream) {
-    if (!mean && !stddev) return VACV_ERR_UNSUPPORTED;  // per-image statistics of a ROI: not built
-    if (!mean || !stddev) return VACV_ERR_INVALID_ARG;
-    Img sm, d;
-    int st = load(src, sm);
-    if (st) return st;
-    if ((st = load(dst, d))) return st;
-    if (sm.c != d.c) return VACV_ERR_INVALID_ARG;  // mean / stddev hold the source's c values
     NormSpec ns;
-    if ((st = norm_spec(d, mean, stddev, ns))) return st;
+    const int st = roi_norm_spec(src, dst, mean, stddev, false, ns);
+    if (st) return st;
     return crop_resize_rois_impl(src, dst, rects, src_index, interpolation, mode, &ns, (hipStream_t)stream);
 }
 
@@ -1129,21 +1112,27 @@ int vacv_mean_stddev(const vacv_image* src_d, float* mean, float* stddev, void* 
 
 int vacv_resize_normalize(const vacv_image* src, const vacv_image* dst, int interpolation, int mode,
                           const float* mean, const float* stddev, void* stream) {
-    ResizeCtx c{src, dst, interpolation, mode};
-    return fused_normalize(dst, mean, stddev, (hipStream_t)stream, resize_pass, &c);
+    hipStream_t s = (hipStream_t)stream;
+    return fused_normalize(dst, mean, stddev, s, [&](int out, const NormSpec* ns) {
+        return resize_impl(src, dst, interpolation, mode, out, ns, s);
+    });
 }
 
 int vacv_warp_affine_normalize(const vacv_image* src, const vacv_image* dst, const float m[6], int flags,
                                int border_mode, const double border_value[4], const float* mean, const float* stddev,
                                void* stream) {
-    WarpCtx c{src, dst, m, flags, border_mode, border_value};
-    return fused_normalize(dst, mean, stddev, (hipStream_t)stream, warp_pass, &c);
+    hipStream_t s = (hipStream_t)stream;
+    return fused_normalize(dst, mean, stddev, s, [&](int out, const NormSpec* ns) {
+        return warp_impl(src, dst, m, flags, border_mode, border_value, out, ns, s);
+    });
 }
 
 int vacv_cvt_color_normalize(const vacv_image* src, const vacv_image* dst, int code, const float* mean,
                              const float* stddev, void* stream) {
-    ColorCtx c{src, dst, code};
-    return fused_normalize(dst, mean, stddev, (hipStream_t)stream, color_pass, &c);
+    hipStream_t s = (hipStream_t)stream;
+    return fused_normalize(dst, mean, stddev, s, [&](int out, const NormSpec* ns) {
+        return color_impl(src, dst, code, out, ns, s);
+    });
 }
 
 int vacv_cvt_color_resize(const vacv_image* src, const vacv_image* dst, int code, int interpolation, int mode,
@@ -1155,8 +1144,10 @@ int vacv_cvt_color_resize(const vacv_image* src, const vacv_image* dst, int code
 
 int vacv_cvt_color_resize_normalize(const vacv_image* src, const vacv_image* dst, int code, int interpolation,
                                     int mode, const float* mean, const float* stddev, void* stream) {
-    YuvResizeCtx c{src, dst, code, interpolation, mode};
-    return fused_normalize(dst, mean, stddev, (hipStream_t)stream, yuv_resize_pass, &c);
+    hipStream_t s = (hipStream_t)stream;
+    return fused_normalize(dst, mean, stddev, s, [&](int out, const NormSpec* ns) {
+        return yuv_resize_impl(src, dst, code, interpolation, mode, out, ns, s);
+    });
 }
 
 int vacv_cvt_color_warp_affine_rois(const vacv_image* src, const vacv_image* dst, int code, const float* m,
@@ -1170,14 +1161,9 @@ int vacv_cvt_color_warp_affine_rois_normalize(const vacv_image* src, const vacv_
                                               const int32_t* src_index, int flags, int border_mode,
                                               const double border_value[4], const float* mean, const float* stddev,
                                               void* stream) {
-    if (!mean && !stddev) return VACV_ERR_UNSUPPORTED;  // per-image statistics of a ROI: not built
-    if (!mean || !stddev) return VACV_ERR_INVALID_ARG;
-    Img sm, d;
-    int st = load2(src, dst, sm, d);
-    if (st) return st;
-    if (d.c != 3) return VACV_ERR_INVALID_ARG;  // mean / stddev hold the decoded frame's 3 values
     NormSpec ns;
-    if ((st = norm_spec(d, mean, stddev, ns))) return st;
+    const int st = roi_norm_spec(src, dst, mean, stddev, true, ns);
+    if (st) return st;
     return yuv_rois_impl(src, dst, code, m, src_index, flags, border_mode, border_value, &ns, (hipStream_t)stream);
 }
 

@@ -360,18 +360,69 @@ void warp_affine(const std::vector<Tensor>& src, std::vector<Tensor>& dst, const
 
 namespace {
 
-// waits for the stream before the staged operands of an early exit go away
-struct SyncOnExit {
+// The operands of one launch for all crops of a frame, on a leased stream: the
+// frame and the per-crop parameters go to HBM once (host operands through the
+// pinned pool, a device frame stays where it is), the kernel writes the crops
+// back to back into scratch, and each crop is copied into its own dst tensor
+// (placement of src).
+struct RoiStage {
+    const char* fn;
+    detail::Lease lease;
     hipStream_t s;
-    ~SyncOnExit() { (void)hipStreamSynchronize(s); }
+    Tensor pinned;  // the per-crop parameters on the host
+    bool queued = false;
+    unsigned char* crops = nullptr;
+    size_t roi_bytes = 0;
+
+    RoiStage(const char* fn_, const Tensor& src) : fn(fn_), lease(detail::compute_device(src)), s(lease.stream()) {}
+    // waits for the stream before the staged operands of an early exit go away
+    ~RoiStage() {
+        if (queued) (void)hipStreamSynchronize(s);
+    }
+    // k 4-byte values for each of n crops, contiguous, in pinned memory: the caller fills them
+    void* host_params(int k, size_t n, const char* oom) {
+        pinned = Tensor(k, (int)n, 1, FP32, NCHW);
+        if (!pinned.data) fail(fn, oom);
+        return pinned.data;
+    }
+    // ... and they go to scratch slot 1
+    void* params() {
+        queued = true;
+        void* d = lease.scratch(1, pinned.len());
+        detail::check_hip(fn, hipMemcpyAsync(d, pinned.data, pinned.len(), hipMemcpyHostToDevice, s));
+        return d;
+    }
+    // the frame where the kernel reads it: a host frame goes to scratch slot 0
+    vacv_image frame(const Tensor& src) {
+        void* d = src.data;
+        if (!src.on_device()) {
+            d = lease.scratch(0, src.len());
+            detail::check_hip(fn, hipMemcpyAsync(d, src.data, src.len(), hipMemcpyHostToDevice, s));
+        }
+        return detail::describe(src, d);
+    }
+    // n crops back to back: scratch slot 2
+    vacv_image out(size_t n, VSize size, int c, DType dtype) {
+        roi_bytes = (size_t)size.w * size.h * c * dtype_size(dtype);
+        crops = static_cast<unsigned char*>(lease.scratch(2, n * roi_bytes));
+        return vacv_image{crops, (int)n, size.w, size.h, c, dtype, NHWC, 0, 0, 0};  // pitches 0 = dense
+    }
+    // every crop into a tensor of its own with src's placement, then wait
+    void scatter(std::vector<Tensor>& dst, const vacv_image& d, const Tensor& src) {
+        dst.resize(d.n);
+        for (size_t i = 0; i < dst.size(); ++i) {
+            dst[i].create_on(src.device(), d.w, d.h, d.c, static_cast<DType>(d.dtype), NHWC);
+            if (roi_bytes > 0 && !dst[i].data) fail(fn, "out of memory creating the output tensor");
+            detail::check_hip(fn, hipMemcpyAsync(dst[i].data, crops + i * roi_bytes, roi_bytes,
+                                                 dst[i].on_device() ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+        }
+        lease.sync(fn);
+    }
 };
 
-// One launch for all crops: the frame and the matrices go to HBM once (host
-// operands through the pinned pool, device operands stay where they are), the
-// kernel writes the crops back to back into scratch, and each crop is copied
-// into its own dst tensor (placement of src).  yuv_code != 0: src is a YUV420sp
-// frame and the crops are taken from its decoded (w, h, 3) image
-// (vacv_cvt_color_warp_affine_rois).
+// One launch for all crops (RoiStage); each matrix is taken from where it
+// lives.  yuv_code != 0: src is a YUV420sp frame and the crops are taken from
+// its decoded (w, h, 3) image (vacv_cvt_color_warp_affine_rois).
 void warp_rois_into(const char* fn, const Tensor& src, std::vector<Tensor>& dst, const std::vector<Tensor>& M,
                     VSize dsize, int flags, int borderMode, const VScalar& bv, const Stats* stats, int yuv_code = 0) {
     if (src.empty()) fail(fn, "empty input tensor");
@@ -387,46 +438,24 @@ void warp_rois_into(const char* fn, const Tensor& src, std::vector<Tensor>& dst,
     if (dsize.w < 1 || dsize.h < 1) fail(fn, "dsize must be positive");
     if (M.empty()) fail(fn, "empty matrix list");
     const size_t n = M.size();
-    const DType odt = stats ? FP32 : src.dtype;
-    const int oc = yuv_code ? 3 : src.c;
-    const size_t roi_bytes = (size_t)dsize.w * dsize.h * oc * dtype_size(odt);
     if (n > 0x7FFFFFFFu) fail(fn, "too many matrices");
-    detail::Lease lease(detail::compute_device(src));
+    RoiStage st(fn, src);
     for (const Tensor& m : M) {
         if (m.dtype != FP32 || m.size() != 6) fail(fn, "every M must be a 2x3 FP32 tensor");
-        if (m.on_device() && m.device() != lease.device()) fail(fn, "operands live on different devices");
+        if (m.on_device() && m.device() != st.lease.device()) fail(fn, "operands live on different devices");
     }
-    if (src.on_device() && src.device() != lease.device()) fail(fn, "operands live on different devices");
-    const hipStream_t s = lease.stream();
-
-    Tensor mh(6, (int)n, 1, FP32, NCHW);  // the host matrices, contiguous, in pinned memory
-    if (!mh.data) fail(fn, "out of memory staging the matrices");
-    float* mp = static_cast<float*>(mh.data);
+    if (src.on_device() && src.device() != st.lease.device()) fail(fn, "operands live on different devices");
+    const hipStream_t s = st.s;
+    float* mp = static_cast<float*>(st.host_params(6, n, "out of memory staging the matrices"));
     std::memset(mp, 0, n * 6 * sizeof(float));
     for (size_t i = 0; i < n; ++i)
         if (!M[i].on_device()) std::memcpy(mp + 6 * i, M[i].data, 6 * sizeof(float));
-    SyncOnExit guard{s};
-    float* dm = static_cast<float*>(lease.scratch(1, n * 6 * sizeof(float)));
-    detail::check_hip(fn, hipMemcpyAsync(dm, mp, n * 6 * sizeof(float), hipMemcpyHostToDevice, s));
-    for (size_t i = 0; i < n; ++i)
+    float* dm = static_cast<float*>(st.params());
+    for (size_t i = 0; i < n; ++i)  // over the zeros of its place
         if (M[i].on_device())
             detail::check_hip(fn, hipMemcpyAsync(dm + 6 * i, M[i].data, 6 * sizeof(float), hipMemcpyDeviceToDevice, s));
-    void* sdev = src.data;
-    if (!src.on_device()) {
-        sdev = lease.scratch(0, src.len());
-        detail::check_hip(fn, hipMemcpyAsync(sdev, src.data, src.len(), hipMemcpyHostToDevice, s));
-    }
-    unsigned char* dout = static_cast<unsigned char*>(lease.scratch(2, n * roi_bytes));
-
-    const vacv_image sd = detail::describe(src, sdev);
-    vacv_image dd{};
-    dd.data = dout;
-    dd.n = (int)n;
-    dd.w = dsize.w;
-    dd.h = dsize.h;
-    dd.c = oc;
-    dd.dtype = odt;
-    dd.layout = NHWC;
+    const vacv_image sd = st.frame(src);
+    const vacv_image dd = st.out(n, dsize, yuv_code ? 3 : src.c, stats ? FP32 : src.dtype);
     const double border[4] = {bv.v0, bv.v1, bv.v2, bv.v3};
     if (yuv_code && stats)
         detail::check(fn, vacv_cvt_color_warp_affine_rois_normalize(&sd, &dd, yuv_code, dm, nullptr, flags, borderMode,
@@ -438,14 +467,7 @@ void warp_rois_into(const char* fn, const Tensor& src, std::vector<Tensor>& dst,
                                                           stats->s(), s));
     else
         detail::check(fn, vacv_warp_affine_rois(&sd, &dd, dm, nullptr, flags, borderMode, border, s));
-    dst.resize(n);
-    for (size_t i = 0; i < n; ++i) {
-        dst[i].create_on(src.device(), dsize.w, dsize.h, oc, odt, NHWC);
-        if (roi_bytes > 0 && !dst[i].data) fail(fn, "out of memory creating the output tensor");
-        detail::check_hip(fn, hipMemcpyAsync(dst[i].data, dout + i * roi_bytes, roi_bytes,
-                                             dst[i].on_device() ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
-    }
-    lease.sync(fn);
+    st.scatter(dst, dd, src);
 }
 
 }  // namespace
@@ -482,9 +504,7 @@ void cvt_color_warp_affine_normalize(const Tensor& yuv, std::vector<Tensor>& dst
 
 namespace {
 
-// One launch for all crops, staged as warp_rois_into stages its operands: the
-// frame and the truncated rects go to HBM once, the kernel writes the crops
-// back to back into scratch, and each crop is copied into its own dst tensor.
+// One launch for all crops (RoiStage) of the rects, truncated as crop() does.
 void crop_resize_into(const char* fn, const Tensor& src, std::vector<Tensor>& dst, const std::vector<VRect>& rects,
                       VSize dsize, int interpolation, const Stats* stats) {
     if (src.empty()) fail(fn, "empty input tensor");
@@ -495,15 +515,10 @@ void crop_resize_into(const char* fn, const Tensor& src, std::vector<Tensor>& ds
     if (rects.empty()) fail(fn, "empty rect list");
     const size_t n = rects.size();
     if (n > 0x7FFFFFFFu) fail(fn, "too many rects");
-    const DType odt = stats ? FP32 : src.dtype;
-    const size_t roi_bytes = (size_t)dsize.w * dsize.h * src.c * dtype_size(odt);
-    detail::Lease lease(detail::compute_device(src));
-    if (src.on_device() && src.device() != lease.device()) fail(fn, "operands live on different devices");
-    const hipStream_t s = lease.stream();
+    RoiStage st(fn, src);
+    if (src.on_device() && src.device() != st.lease.device()) fail(fn, "operands live on different devices");
 
-    Tensor rh(4, (int)n, 1, FP32, NCHW);  // the int32 rects, contiguous, in pinned memory (4-byte elements)
-    if (!rh.data) fail(fn, "out of memory staging the rects");
-    int32_t* rp = static_cast<int32_t*>(rh.data);
+    int32_t* rp = static_cast<int32_t*>(st.host_params(4, n, "out of memory staging the rects"));
     for (size_t i = 0; i < n; ++i) {
         // crop.cpp:128-131
         const int left = static_cast<int>(rects[i].left), top = static_cast<int>(rects[i].top);
@@ -516,38 +531,15 @@ void crop_resize_into(const char* fn, const Tensor& src, std::vector<Tensor>& ds
         rp[4 * i + 2] = cw;
         rp[4 * i + 3] = ch;
     }
-    SyncOnExit guard{s};
-    int32_t* dr = static_cast<int32_t*>(lease.scratch(1, n * 4 * sizeof(int32_t)));
-    detail::check_hip(fn, hipMemcpyAsync(dr, rp, n * 4 * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    void* sdev = src.data;
-    if (!src.on_device()) {
-        sdev = lease.scratch(0, src.len());
-        detail::check_hip(fn, hipMemcpyAsync(sdev, src.data, src.len(), hipMemcpyHostToDevice, s));
-    }
-    unsigned char* dout = static_cast<unsigned char*>(lease.scratch(2, n * roi_bytes));
-
-    const vacv_image sd = detail::describe(src, sdev);
-    vacv_image dd{};
-    dd.data = dout;
-    dd.n = (int)n;
-    dd.w = dsize.w;
-    dd.h = dsize.h;
-    dd.c = src.c;
-    dd.dtype = odt;
-    dd.layout = NHWC;
+    const int32_t* dr = static_cast<const int32_t*>(st.params());
+    const vacv_image sd = st.frame(src);
+    const vacv_image dd = st.out(n, dsize, src.c, stats ? FP32 : src.dtype);
     if (stats)
         detail::check(fn, vacv_crop_resize_rois_normalize(&sd, &dd, dr, nullptr, interpolation, VACV_LINEAR_REFERENCE,
-                                                          stats->m(), stats->s(), s));
+                                                          stats->m(), stats->s(), st.s));
     else
-        detail::check(fn, vacv_crop_resize_rois(&sd, &dd, dr, nullptr, interpolation, VACV_LINEAR_REFERENCE, s));
-    dst.resize(n);
-    for (size_t i = 0; i < n; ++i) {
-        dst[i].create_on(src.device(), dsize.w, dsize.h, src.c, odt, NHWC);
-        if (roi_bytes > 0 && !dst[i].data) fail(fn, "out of memory creating the output tensor");
-        detail::check_hip(fn, hipMemcpyAsync(dst[i].data, dout + i * roi_bytes, roi_bytes,
-                                             dst[i].on_device() ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
-    }
-    lease.sync(fn);
+        detail::check(fn, vacv_crop_resize_rois(&sd, &dd, dr, nullptr, interpolation, VACV_LINEAR_REFERENCE, st.s));
+    st.scatter(dst, dd, src);
 }
 
 }  // namespace

@@ -258,21 +258,36 @@ def _device_array(a, dtype: torch.dtype, device, what: str) -> torch.Tensor:
     return a
 
 
-def _rois_args(src: torch.Tensor, ms, src_index):
-    s4 = _as4d(src, NHWC)
-    ms = _device_array(ms, torch.float32, s4.device, "ms")
-    if not (ms.dim() == 2 and ms.shape[1] == 6) and not (ms.dim() == 3 and tuple(ms.shape[1:]) == (2, 3)):
-        raise ValueError(f"ms must have shape (n, 6) or (n, 2, 3), got {tuple(ms.shape)}")
-    n = ms.shape[0]
+def _roi_batch(src4, arr, what, dtype, shape_ok, shape_msg, empty_msg, src_index):
+    """A batched-ROI call's per-ROI array (one row per ROI) and src_index, checked against the frames src4."""
+    arr = _device_array(arr, dtype, src4.device, what)
+    if not shape_ok(arr):
+        raise ValueError(f"{what} must have shape {shape_msg}, got {tuple(arr.shape)}")
+    n = arr.shape[0]
     if n < 1:
-        raise ValueError("ms holds no matrix")
+        raise ValueError(empty_msg)
     if src_index is not None:
-        src_index = _device_array(src_index, torch.int32, s4.device, "src_index")
+        src_index = _device_array(src_index, torch.int32, src4.device, "src_index")
         if tuple(src_index.shape) != (n,):
             raise ValueError(f"src_index must have shape ({n},), got {tuple(src_index.shape)}")
-    elif s4.shape[0] not in (1, n):
-        raise ValueError(f"without src_index, src must hold 1 or {n} images, not {s4.shape[0]}")
-    return s4, ms, src_index, n
+    elif src4.shape[0] not in (1, n):
+        raise ValueError(f"without src_index, src must hold 1 or {n} images, not {src4.shape[0]}")
+    return src4, arr, src_index, n
+
+
+# _roi_batch's (what, dtype, shape_ok, shape_msg, empty_msg) of the two kinds of per-ROI array
+_MS = ("ms", torch.float32,
+       lambda a: (a.dim() == 2 and a.shape[1] == 6) or (a.dim() == 3 and tuple(a.shape[1:]) == (2, 3)),
+       "(n, 6) or (n, 2, 3)", "ms holds no matrix")
+_RECTS = ("rects", torch.int32, lambda a: a.dim() == 2 and a.shape[1] == 4, "(n, 4)", "rects holds no rect")
+
+
+def _idx_ptr(src_index):
+    return src_index.data_ptr() if src_index is not None else None
+
+
+def _border(border_value):
+    return _dptr((list(border_value) + [0, 0, 0, 0])[:4])  # the C side reads four
 
 
 def warp_affine_rois(src: torch.Tensor, ms, w: int, h: int, src_index=None, flags: int = INTER_LINEAR,
@@ -283,13 +298,13 @@ def warp_affine_rois(src: torch.Tensor, ms, w: int, h: int, src_index=None, flag
     or (n, 2, 3) float32 device tensor; src_index: (n,) int32 device tensor, or
     None (one frame for all, or frame i for ROI i).  Both are read by the
     kernel when it runs on `stream`, not by this call.  Returns (n, h, w, c)."""
-    s4, ms, src_index, n = _rois_args(src, ms, src_index)
+    s4, ms, src_index, n = _roi_batch(_as4d(src, NHWC), ms, *_MS, src_index)
     if out is None:
         out = torch.empty((n, h, w, s4.shape[3]), dtype=src.dtype, device=src.device)
-    bv, bp = _dptr((list(border_value) + [0, 0, 0, 0])[:4])  # the C side reads four
+    bv, bp = _border(border_value)
     check("vacv_warp_affine_rois", L.load().vacv_warp_affine_rois(
         ctypes.byref(describe(s4, NHWC)), ctypes.byref(describe(out, NHWC)), ms.data_ptr(),
-        src_index.data_ptr() if src_index is not None else None, flags, border_mode, bp, _stream(stream)))
+        _idx_ptr(src_index), flags, border_mode, bp, _stream(stream)))
     return out
 
 
@@ -299,19 +314,18 @@ def warp_affine_rois_normalize(src: torch.Tensor, ms, w: int, h: int, mean, std,
                                stream=None) -> torch.Tensor:
     """warp_affine_rois with the fused normalize: fp32 (n, h, w, c), or planar
     (n, c, h, w) with out_layout=NCHW (c = 3 or 1), the model-input layout."""
-    s4, ms, src_index, n = _rois_args(src, ms, src_index)
+    s4, ms, src_index, n = _roi_batch(_as4d(src, NHWC), ms, *_MS, src_index)
     c = s4.shape[3]
     if mean is None or std is None:
         raise ValueError("warp_affine_rois_normalize needs mean and stddev (no per-image statistics for ROIs)")
     if out is None:
         out = torch.empty((n, h, w, c) if out_layout == NHWC else (n, c, h, w), dtype=torch.float32,
                           device=src.device)
-    bv, bp = _dptr((list(border_value) + [0, 0, 0, 0])[:4])  # the C side reads four
+    bv, bp = _border(border_value)
     (ma, meanp), (sa, stdp) = _meanstd(mean, std, c)
     check("vacv_warp_affine_rois_normalize", L.load().vacv_warp_affine_rois_normalize(
         ctypes.byref(describe(s4, NHWC)), ctypes.byref(describe(out, out_layout)), ms.data_ptr(),
-        src_index.data_ptr() if src_index is not None else None, flags, border_mode, bp, meanp, stdp,
-        _stream(stream)))
+        _idx_ptr(src_index), flags, border_mode, bp, meanp, stdp, _stream(stream)))
     return out
 
 
@@ -348,23 +362,6 @@ def rects_from_boxes(boxes: torch.Tensor) -> torch.Tensor:
     return torch.cat([lt, boxes[:, 2:] - lt], 1).to(torch.int32).contiguous()
 
 
-def _crop_rois_args(src: torch.Tensor, rects, src_index):
-    s4 = _as4d(src, NHWC)
-    rects = _device_array(rects, torch.int32, s4.device, "rects")
-    if rects.dim() != 2 or rects.shape[1] != 4:
-        raise ValueError(f"rects must have shape (n, 4), got {tuple(rects.shape)}")
-    n = rects.shape[0]
-    if n < 1:
-        raise ValueError("rects holds no rect")
-    if src_index is not None:
-        src_index = _device_array(src_index, torch.int32, s4.device, "src_index")
-        if tuple(src_index.shape) != (n,):
-            raise ValueError(f"src_index must have shape ({n},), got {tuple(src_index.shape)}")
-    elif s4.shape[0] not in (1, n):
-        raise ValueError(f"without src_index, src must hold 1 or {n} images, not {s4.shape[0]}")
-    return s4, rects, src_index, n
-
-
 def crop_resize_rois(src: torch.Tensor, rects, w: int, h: int, src_index=None, mode: int = LINEAR_REFERENCE,
                      out=None, stream=None) -> torch.Tensor:
     """Many upright crops in one launch: out[i] = resize(crop(src[src_index[i]],
@@ -375,12 +372,12 @@ def crop_resize_rois(src: torch.Tensor, rects, w: int, h: int, src_index=None, m
     (n,) int32 device tensor, or None (one frame for all, or frame i for ROI i).
     Both are read by the kernel when it runs on `stream`, not by this call; an
     invalid rect or index gives a ROI of zeros.  Returns (n, h, w, c)."""
-    s4, rects, src_index, n = _crop_rois_args(src, rects, src_index)
+    s4, rects, src_index, n = _roi_batch(_as4d(src, NHWC), rects, *_RECTS, src_index)
     if out is None:
         out = torch.empty((n, h, w, s4.shape[3]), dtype=src.dtype, device=src.device)
     check("vacv_crop_resize_rois", L.load().vacv_crop_resize_rois(
         ctypes.byref(describe(s4, NHWC)), ctypes.byref(describe(out, NHWC)), rects.data_ptr(),
-        src_index.data_ptr() if src_index is not None else None, INTER_LINEAR, mode, _stream(stream)))
+        _idx_ptr(src_index), INTER_LINEAR, mode, _stream(stream)))
     return out
 
 
@@ -389,7 +386,7 @@ def crop_resize_rois_normalize(src: torch.Tensor, rects, w: int, h: int, mean, s
                                stream=None) -> torch.Tensor:
     """crop_resize_rois with the fused normalize: fp32 (n, h, w, c), or planar
     (n, c, h, w) with layout=NCHW (c = 3 or 1), the model-input layout."""
-    s4, rects, src_index, n = _crop_rois_args(src, rects, src_index)
+    s4, rects, src_index, n = _roi_batch(_as4d(src, NHWC), rects, *_RECTS, src_index)
     c = s4.shape[3]
     if mean is None or std is None:
         raise ValueError("crop_resize_rois_normalize needs mean and stddev (no per-image statistics for ROIs)")
@@ -398,16 +395,19 @@ def crop_resize_rois_normalize(src: torch.Tensor, rects, w: int, h: int, mean, s
     (ma, meanp), (sa, stdp) = _meanstd(mean, std, c)
     check("vacv_crop_resize_rois_normalize", L.load().vacv_crop_resize_rois_normalize(
         ctypes.byref(describe(s4, NHWC)), ctypes.byref(describe(out, layout)), rects.data_ptr(),
-        src_index.data_ptr() if src_index is not None else None, INTER_LINEAR, mode, meanp, stdp, _stream(stream)))
+        _idx_ptr(src_index), INTER_LINEAR, mode, meanp, stdp, _stream(stream)))
     return out
 
 
 # ---------------------------------------------------------------------------
 # colour
 
+def _yuv4(yuv: torch.Tensor) -> torch.Tensor:
+    return yuv if yuv.dim() == 3 else yuv.unsqueeze(0)
+
+
 def _yuv_desc(yuv: torch.Tensor) -> VacvImage:
-    y4 = yuv if yuv.dim() == 3 else yuv.unsqueeze(0)
-    return describe(y4.unsqueeze(-1), NHWC)
+    return describe(_yuv4(yuv).unsqueeze(-1), NHWC)
 
 
 _DCN4 = (L.COLOR_YUV2RGBA_NV12, L.COLOR_YUV2BGRA_NV12, L.COLOR_YUV2RGBA_NV21, L.COLOR_YUV2BGRA_NV21)
@@ -419,14 +419,14 @@ def cvt_color(yuv: torch.Tensor, code: int = L.COLOR_YUV2BGR_NV21, out=None, str
     COLOR_GRAY2BGR: (n, h, w) u8/fp32 -> (n, h, w, 3) of the same dtype.
     `out` (optional): a preallocated output of that shape."""
     if code == L.COLOR_GRAY2BGR:
-        g4 = yuv if yuv.dim() == 3 else yuv.unsqueeze(0)
+        g4 = _yuv4(yuv)
         if out is None:
             out = torch.empty(tuple(g4.shape) + (3,), dtype=g4.dtype, device=yuv.device)
         out = out if out.dim() == 4 else out.unsqueeze(0)
         check("vacv_cvt_color", L.load().vacv_cvt_color(ctypes.byref(describe(g4.unsqueeze(-1), NHWC)),
                                                         ctypes.byref(describe(out, NHWC)), code, _stream(stream)))
         return out if yuv.dim() == 3 else out[0]
-    y4 = yuv if yuv.dim() == 3 else yuv.unsqueeze(0)
+    y4 = _yuv4(yuv)
     n, hh, w = y4.shape
     if out is None:
         out = torch.empty((n, hh // 3 * 2, w, 4 if code in _DCN4 else 3), dtype=torch.uint8, device=yuv.device)
@@ -438,7 +438,7 @@ def cvt_color(yuv: torch.Tensor, code: int = L.COLOR_YUV2BGR_NV21, out=None, str
 
 def cvt_color_normalize(yuv: torch.Tensor, code: int = L.COLOR_YUV2BGR_NV21, mean=None, std=None, out=None,
                         stream=None) -> torch.Tensor:
-    y4 = yuv if yuv.dim() == 3 else yuv.unsqueeze(0)
+    y4 = _yuv4(yuv)
     n, hh, w = y4.shape
     if out is None:
         out = torch.empty((n, hh // 3 * 2, w, 3), dtype=torch.float32, device=yuv.device)
@@ -455,7 +455,7 @@ def cvt_color_resize(yuv: torch.Tensor, w: int, h: int, code: int = L.COLOR_YUV2
     """cvt_color -> resize(INTER_LINEAR) [-> change_dtype(FP32)] [-> change_layout]
     (cvt_color.cpp:39-157, resize_naive.cpp:10-68) in one kernel:
     (n, h_in*3/2, w_in) u8 -> (n, h, w, 3) NHWC or (n, 3, h, w) NCHW."""
-    y4 = yuv if yuv.dim() == 3 else yuv.unsqueeze(0)
+    y4 = _yuv4(yuv)
     n = y4.shape[0]
     if out is None:
         shape = (n, h, w, 3) if layout == NHWC else (n, 3, h, w)
@@ -473,7 +473,7 @@ def cvt_color_resize_normalize(yuv: torch.Tensor, w: int, h: int, mean=None, std
     fp32, normalize((x - mean) / (std + 1e-6)), change_layout -- one kernel.
     Default layout NCHW (planar fp32).  mean/std None = per-image stats of
     the resized image (two passes)."""
-    y4 = yuv if yuv.dim() == 3 else yuv.unsqueeze(0)
+    y4 = _yuv4(yuv)
     n = y4.shape[0]
     if out is None:
         shape = (n, h, w, 3) if layout == NHWC else (n, 3, h, w)
@@ -494,14 +494,14 @@ def cvt_color_warp_affine_rois(yuv: torch.Tensor, ms, w: int, h: int, code: int 
     (h_in*3/2, w_in) frame; ms / src_index as warp_affine_rois takes them
     (device tensors, read by the kernel when it runs on `stream`);
     border_value in the decoded channel order.  Returns (n, h, w, 3) u8."""
-    y4 = yuv if yuv.dim() == 3 else yuv.unsqueeze(0)
-    _, ms, src_index, n = _rois_args(y4.unsqueeze(-1), ms, src_index)
+    y4 = _yuv4(yuv)
+    _, ms, src_index, n = _roi_batch(_as4d(y4.unsqueeze(-1), NHWC), ms, *_MS, src_index)
     if out is None:
         out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=yuv.device)
-    bv, bp = _dptr((list(border_value) + [0, 0, 0, 0])[:4])  # the C side reads four
+    bv, bp = _border(border_value)
     check("vacv_cvt_color_warp_affine_rois", L.load().vacv_cvt_color_warp_affine_rois(
         ctypes.byref(_yuv_desc(y4)), ctypes.byref(describe(out, NHWC)), code, ms.data_ptr(),
-        src_index.data_ptr() if src_index is not None else None, flags, border_mode, bp, _stream(stream)))
+        _idx_ptr(src_index), flags, border_mode, bp, _stream(stream)))
     return out
 
 
@@ -511,18 +511,17 @@ def cvt_color_warp_affine_rois_normalize(yuv: torch.Tensor, ms, w: int, h: int, 
                                          border_value=(0, 0, 0, 0), out=None, stream=None) -> torch.Tensor:
     """cvt_color_warp_affine_rois with the fused normalize: fp32 (n, h, w, 3),
     or planar (n, 3, h, w) with layout=NCHW, the model-input layout."""
-    y4 = yuv if yuv.dim() == 3 else yuv.unsqueeze(0)
-    _, ms, src_index, n = _rois_args(y4.unsqueeze(-1), ms, src_index)
+    y4 = _yuv4(yuv)
+    _, ms, src_index, n = _roi_batch(_as4d(y4.unsqueeze(-1), NHWC), ms, *_MS, src_index)
     if mean is None or std is None:
         raise ValueError("cvt_color_warp_affine_rois_normalize needs mean and stddev (no per-image statistics for ROIs)")
     if out is None:
         out = torch.empty((n, h, w, 3) if layout == NHWC else (n, 3, h, w), dtype=torch.float32, device=yuv.device)
-    bv, bp = _dptr((list(border_value) + [0, 0, 0, 0])[:4])  # the C side reads four
+    bv, bp = _border(border_value)
     (ma, meanp), (sa, stdp) = _meanstd(mean, std, 3)
     check("vacv_cvt_color_warp_affine_rois_normalize", L.load().vacv_cvt_color_warp_affine_rois_normalize(
         ctypes.byref(_yuv_desc(y4)), ctypes.byref(describe(out, layout)), code, ms.data_ptr(),
-        src_index.data_ptr() if src_index is not None else None, flags, border_mode, bp, meanp, stdp,
-        _stream(stream)))
+        _idx_ptr(src_index), flags, border_mode, bp, meanp, stdp, _stream(stream)))
     return out
 
 
