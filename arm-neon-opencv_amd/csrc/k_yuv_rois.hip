@@ -30,23 +30,6 @@
 namespace vacv {
 namespace {
 
-// One tap: Y and its chroma pair (byte 0 and byte 1 of `pair`, in memory
-// order) to the three output channels, cvt_color.cpp:76-86 as color_kernel
-__device__ __forceinline__ void decode_tap(int Y, uint32_t pair, bool v_first, bool rgb, int (&c)[3]) {
-    const int b0 = (int)(pair & 0xFFu), b1 = (int)((pair >> 8) & 0xFFu);
-    const int v = v_first ? b0 : b1;
-    const int u = v_first ? b1 : b0;
-    const Chroma ch = chroma_terms(u, v);
-    const int R = clamp_u8(Y + ch.ra), G = clamp_u8(Y - ch.ga), B = clamp_u8(Y + ch.ba);
-    c[0] = rgb ? R : B;
-    c[1] = G;
-    c[2] = rgb ? B : R;
-}
-
-__device__ __forceinline__ uint32_t load_u8(const Rsrc& rs, uint32_t off) {
-    return (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(rs.r, (int)off, 0, 0);
-}
-
 // The decoded pixel (x, y) of the frame behind rs (x < w, y < h): three byte loads
 __device__ __forceinline__ void decoded_pixel(const Rsrc& rs, uint32_t rp, int h, int x, int y, bool v_first, bool rgb,
                                               int (&c)[3]) {

@@ -1,7 +1,9 @@
 // roi_tile.hpp -- the tiling helpers of the ROI kernels (k_warp_rois.hip,
-// k_yuv_rois.hip, k_crop_resize_rois.hip): a workgroup owns kRoiTile consecutive row-major pixels of
-// one ROI, lays its band out in LDS at the destination's offset modulo 16 and
-// copies it out in the widest stores the alignment allows.
+// k_yuv_rois.hip, k_crop_resize_rois.hip, k_yuv_crop_resize_rois.hip): a
+// workgroup owns kRoiTile consecutive row-major pixels of one ROI, lays its
+// band out in LDS at the destination's offset modulo 16 and copies it out in
+// the widest stores the alignment allows.  The two YUV kernels share the
+// decode of one tap.
 #pragma once
 
 #include "vacv_device.hpp"
@@ -34,6 +36,23 @@ __device__ __forceinline__ void load_f32(const Rsrc& rs, uint32_t off, float (&v
 #pragma unroll
     for (int i = 0; i < N; ++i)
         v[i] = __builtin_bit_cast(float, (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs.r, (int)(off + 4u * i), 0, 0));
+}
+
+// One tap: Y and its chroma pair (byte 0 and byte 1 of `pair`, in memory
+// order) to the three output channels, cvt_color.cpp:76-86 as color_kernel
+__device__ __forceinline__ void decode_tap(int Y, uint32_t pair, bool v_first, bool rgb, int (&c)[3]) {
+    const int b0 = (int)(pair & 0xFFu), b1 = (int)((pair >> 8) & 0xFFu);
+    const int v = v_first ? b0 : b1;
+    const int u = v_first ? b1 : b0;
+    const Chroma ch = chroma_terms(u, v);
+    const int R = clamp_u8(Y + ch.ra), G = clamp_u8(Y - ch.ga), B = clamp_u8(Y + ch.ba);
+    c[0] = rgb ? R : B;
+    c[1] = G;
+    c[2] = rgb ? B : R;
+}
+
+__device__ __forceinline__ uint32_t load_u8(const Rsrc& rs, uint32_t off) {
+    return (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(rs.r, (int)off, 0, 0);
 }
 
 // nbytes from LDS offset `lo` of xch (16-byte aligned) to d, by threads t of

@@ -784,6 +784,45 @@ int yuv_rois_impl(const vacv_image* src_d, const vacv_image* dst_d, int code, co
     return hip_status(launch_yuv_rois(L, s));
 }
 
+// vacv_cvt_color_crop_resize_rois[_normalize]: dst image i = rect rects[i] of
+// the decoded frame src_index[i], resized to dst->w x dst->h
+// (k_yuv_crop_resize_rois.hip).  src as yuv_rois_impl takes it, rects /
+// src_index / interpolation / mode as crop_resize_rois_impl: device arrays,
+// validated for presence only.  ns as yuv_rois_impl.
+int yuv_crop_resize_rois_impl(const vacv_image* src_d, const vacv_image* dst_d, int code, const int32_t* rects,
+                              const int32_t* src_index, int interpolation, int mode, const NormSpec* ns,
+                              hipStream_t s) {
+    Img src, dst;
+    int st = load2(src_d, dst_d, src, dst);
+    if (st) return st;
+    if (!rects) return VACV_ERR_INVALID_ARG;
+    int v_first, rgb;
+    if ((st = color_code(code, v_first, rgb))) return st;
+    if (src.dtype != VACV_INT8 || src.c != 1 || src.layout != VACV_NHWC) return VACV_ERR_INVALID_ARG;
+    const int h = yuv420sp_height(src);
+    if (h < 0) return h;
+    if (dst.c != 3) return VACV_ERR_INVALID_ARG;
+    if (!roi_frames_ok(src, dst, src_index)) return VACV_ERR_INVALID_ARG;
+    if (interpolation != VACV_INTER_LINEAR) return VACV_ERR_UNSUPPORTED;
+    if (mode < VACV_LINEAR_REFERENCE || mode > VACV_LINEAR_OPENCV) return VACV_ERR_INVALID_ARG;
+    bool planar;  // decoded frames are u8 NHWC
+    if ((st = roi_output(dst, VACV_INT8, ns, planar))) return st;
+    YuvCropResizeRoisLaunch L{};
+    L.src = src.data;
+    L.src_img = src.batch;
+    L.src_row = src.row;
+    L.src_bytes = src.row * (src.h - 1) + src.w;
+    roi_fill(L, src, dst, src_index, planar, ns);
+    L.w = src.w;
+    L.h = h;
+    L.rects = rects;
+    L.mode = mode;
+    L.v_first = v_first;
+    L.rgb = rgb;
+    if (!yuv_crop_resize_rois_fits(L)) return VACV_ERR_UNSUPPORTED;
+    return hip_status(launch_yuv_crop_resize_rois(L, s));
+}
+
 // An operator with the fused normalize.  pass(out_kind, ns) queues the operator
 // writing dst: normalized with the given statistics, or (no statistics: those
 // of its own fp32 output, per image) raw fp32, normalized in place afterwards.
@@ -1165,6 +1204,21 @@ int vacv_cvt_color_warp_affine_rois_normalize(const vacv_image* src, const vacv_
     const int st = roi_norm_spec(src, dst, mean, stddev, true, ns);
     if (st) return st;
     return yuv_rois_impl(src, dst, code, m, src_index, flags, border_mode, border_value, &ns, (hipStream_t)stream);
+}
+
+int vacv_cvt_color_crop_resize_rois(const vacv_image* src, const vacv_image* dst, int code, const int32_t* rects,
+                                    const int32_t* src_index, int interpolation, int mode, void* stream) {
+    return yuv_crop_resize_rois_impl(src, dst, code, rects, src_index, interpolation, mode, nullptr,
+                                     (hipStream_t)stream);
+}
+
+int vacv_cvt_color_crop_resize_rois_normalize(const vacv_image* src, const vacv_image* dst, int code,
+                                              const int32_t* rects, const int32_t* src_index, int interpolation,
+                                              int mode, const float* mean, const float* stddev, void* stream) {
+    NormSpec ns;
+    const int st = roi_norm_spec(src, dst, mean, stddev, true, ns);
+    if (st) return st;
+    return yuv_crop_resize_rois_impl(src, dst, code, rects, src_index, interpolation, mode, &ns, (hipStream_t)stream);
 }
 
 int vacv_match_template(const vacv_image* img_d, const vacv_image* tpl_d, const vacv_image* res_d, int method,

@@ -357,6 +357,29 @@ struct YuvRoisLaunch {
 };
 hipError_t launch_yuv_rois(const YuvRoisLaunch& L, hipStream_t s);
 
+// Many upright crops of YUV420sp frames in one launch
+// (k_yuv_crop_resize_rois.hip): ROI i = cvt_color of frame src_index[i], then
+// the bilinear resize of rect rects[i] of the decoded frame with the rect's
+// own taps; both arrays are device memory read by the kernel
+struct YuvCropResizeRoisLaunch {
+    const unsigned char* src;      // Y plane of frame 0
+    int64_t src_img, src_row;      // bytes
+    int64_t src_bytes;             // readable bytes of one frame (Y + chroma rows)
+    PlaneGeom dst;                 // ROI 0; img_pitch between ROIs; planar: plane_pitch between channel planes
+    int n_src, n_roi;
+    int w, h;                      // decoded frame size
+    const int32_t* rects;          // device [n_roi][4]: left, top, width, height in the decoded frame
+    const int32_t* src_index;      // device [n_roi], or null: frame 0 (n_src == 1) or frame i
+    int mode;                      // VACV_LINEAR_*
+    int v_first;                   // NV21
+    int rgb;                       // swap output channel order
+    int out;                       // kOutSame (u8 NHWC) or kOutNorm
+    int planar;                    // fp32 NCHW destination
+    NormSpec norm;
+};
+bool yuv_crop_resize_rois_fits(const YuvCropResizeRoisLaunch& L);  // within the kernel's 32-bit indices
+hipError_t launch_yuv_crop_resize_rois(const YuvCropResizeRoisLaunch& L, hipStream_t s);
+
 struct NormLaunch {                // elementwise normalize
     PlaneGeom src;
     PlaneGeom dst;

@@ -505,9 +505,16 @@ void cvt_color_warp_affine_normalize(const Tensor& yuv, std::vector<Tensor>& dst
 namespace {
 
 // One launch for all crops (RoiStage) of the rects, truncated as crop() does.
+// yuv_code != 0: src is a YUV420sp frame and the rects are taken from its
+// decoded (w, h, 3) image (vacv_cvt_color_crop_resize_rois).
 void crop_resize_into(const char* fn, const Tensor& src, std::vector<Tensor>& dst, const std::vector<VRect>& rects,
-                      VSize dsize, int interpolation, const Stats* stats) {
+                      VSize dsize, int interpolation, const Stats* stats, int yuv_code = 0) {
     if (src.empty()) fail(fn, "empty input tensor");
+    int fw = src.w, fh = src.h;  // what the rects must lie in
+    if (yuv_code) {
+        check_yuv_code(fn, yuv_code);
+        fh = yuv_rows(fn, src);
+    }
     if (src.dtype != INT8 && src.dtype != FP32) fail(fn, "crop_resize takes INT8 or FP32");
     if (src.layout != NHWC) fail(fn, "the crops of one frame take an NHWC frame");
     if (interpolation != INTER_LINEAR) fail(fn, "only INTER_LINEAR is supported for the crops of one frame");
@@ -524,7 +531,7 @@ void crop_resize_into(const char* fn, const Tensor& src, std::vector<Tensor>& ds
         const int left = static_cast<int>(rects[i].left), top = static_cast<int>(rects[i].top);
         const int cw = static_cast<int>(rects[i].width()), ch = static_cast<int>(rects[i].height());
         // what crop() and resize() refuse one by one (the kernel would write zeros)
-        if (cw < 2 || ch < 2 || left < 0 || top < 0 || cw > src.w || left > src.w - cw || ch > src.h || top > src.h - ch)
+        if (cw < 2 || ch < 2 || left < 0 || top < 0 || cw > fw || left > fw - cw || ch > fh || top > fh - ch)
             fail(fn, "every rect must lie inside the image and hold at least 2 x 2 pixels");
         rp[4 * i] = left;
         rp[4 * i + 1] = top;
@@ -533,8 +540,14 @@ void crop_resize_into(const char* fn, const Tensor& src, std::vector<Tensor>& ds
     }
     const int32_t* dr = static_cast<const int32_t*>(st.params());
     const vacv_image sd = st.frame(src);
-    const vacv_image dd = st.out(n, dsize, src.c, stats ? FP32 : src.dtype);
-    if (stats)
+    const vacv_image dd = st.out(n, dsize, yuv_code ? 3 : src.c, stats ? FP32 : src.dtype);
+    if (yuv_code && stats)
+        detail::check(fn, vacv_cvt_color_crop_resize_rois_normalize(&sd, &dd, yuv_code, dr, nullptr, interpolation,
+                                                                    VACV_LINEAR_REFERENCE, stats->m(), stats->s(), st.s));
+    else if (yuv_code)
+        detail::check(fn, vacv_cvt_color_crop_resize_rois(&sd, &dd, yuv_code, dr, nullptr, interpolation,
+                                                          VACV_LINEAR_REFERENCE, st.s));
+    else if (stats)
         detail::check(fn, vacv_crop_resize_rois_normalize(&sd, &dd, dr, nullptr, interpolation, VACV_LINEAR_REFERENCE,
                                                           stats->m(), stats->s(), st.s));
     else
@@ -555,6 +568,20 @@ void crop_resize_normalize(const Tensor& src, std::vector<Tensor>& dst, const st
     const Stats stats = read_stats(fn, mean, stddev, src.c, false);
     if (!stats.m()) fail(fn, "the crops of one frame need mean and stddev (no per-image statistics)");
     crop_resize_into(fn, src, dst, rects, dsize, interpolation, &stats);
+}
+
+void cvt_color_crop_resize(const Tensor& yuv, std::vector<Tensor>& dst, const std::vector<VRect>& rects, int code,
+                           VSize dsize, int interpolation) {
+    crop_resize_into("va_cv::cvt_color_crop_resize", yuv, dst, rects, dsize, interpolation, nullptr, code);
+}
+
+void cvt_color_crop_resize_normalize(const Tensor& yuv, std::vector<Tensor>& dst, const std::vector<VRect>& rects,
+                                     int code, VSize dsize, int interpolation, const Tensor& mean,
+                                     const Tensor& stddev) {
+    static const char* fn = "va_cv::cvt_color_crop_resize_normalize";
+    const Stats stats = read_stats(fn, mean, stddev, 3, false);
+    if (!stats.m()) fail(fn, "the crops of one frame need mean and stddev (no per-image statistics)");
+    crop_resize_into(fn, yuv, dst, rects, dsize, interpolation, &stats, code);
 }
 
 void cvt_color(const std::vector<Tensor>& src, std::vector<Tensor>& dst, int code) {

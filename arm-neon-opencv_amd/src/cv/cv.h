@@ -247,6 +247,18 @@ void crop_resize_normalize(const vision::Tensor& src, std::vector<vision::Tensor
                            const std::vector<vision::VRect>& rects, VSize dsize, int interpolation = INTER_LINEAR,
                            const vision::Tensor& mean = vision::Tensor(),
                            const vision::Tensor& stddev = vision::Tensor());
+/// The same upright crops straight from one YUV420sp frame (w, h*3/2, 1) INT8
+/// NHWC, ONE kernel launch and no decoded frame: dst[i] = resize(crop(
+/// cvt_color(yuv, code), rects[i]), dsize), byte for byte, (w, h, 3) crops.
+/// code: the NV21 / NV12 -> BGR / RGB codes; the rects lie in the decoded frame.
+void cvt_color_crop_resize(const vision::Tensor& yuv, std::vector<vision::Tensor>& dst,
+                           const std::vector<vision::VRect>& rects, int code, VSize dsize,
+                           int interpolation = INTER_LINEAR);
+void cvt_color_crop_resize_normalize(const vision::Tensor& yuv, std::vector<vision::Tensor>& dst,
+                                     const std::vector<vision::VRect>& rects, int code, VSize dsize,
+                                     int interpolation = INTER_LINEAR,
+                                     const vision::Tensor& mean = vision::Tensor(),
+                                     const vision::Tensor& stddev = vision::Tensor());
 void cvt_color(const std::vector<vision::Tensor>& src, std::vector<vision::Tensor>& dst, int code);
 void cvt_color_normalize(const std::vector<vision::Tensor>& src, std::vector<vision::Tensor>& dst, int code,
                          const vision::Tensor& mean = vision::Tensor(),

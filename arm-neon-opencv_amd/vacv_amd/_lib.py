@@ -98,6 +98,8 @@ SIGNATURES = {
     "vacv_cvt_color_resize_normalize": ([_IMG, _IMG, _I, _I, _I, _FP, _FP, _P], _I),
     "vacv_cvt_color_warp_affine_rois": ([_IMG, _IMG, _I, _P, _P, _I, _I, _DP, _P], _I),
     "vacv_cvt_color_warp_affine_rois_normalize": ([_IMG, _IMG, _I, _P, _P, _I, _I, _DP, _FP, _FP, _P], _I),
+    "vacv_cvt_color_crop_resize_rois": ([_IMG, _IMG, _I, _P, _P, _I, _I, _P], _I),
+    "vacv_cvt_color_crop_resize_rois_normalize": ([_IMG, _IMG, _I, _P, _P, _I, _I, _FP, _FP, _P], _I),
     "vacv_stream_synchronize": ([_P], _I),
     "vacv_release_workspace": ([], _I),
     "vacv_match_template": ([_IMG, _IMG, _IMG, _I, _P], _I),
@@ -118,7 +120,8 @@ TUNE = {"RESIZE_DIRECT": 0, "CUBIC_DIRECT": 1, "RESIZE_INTERLEAVE": 2, "DIRECT_X
 # Bumped with every change to a signature or to the tuning enum (3: round 6,
 # after round 5 added LANCZOS_KERNEL under version 2; 4: the ROI warp entry
 # points and vacv_invert_affine_device; 5: the ROI warp from YUV420sp frames).
-# An added export alone does not bump it (vacv_crop_resize_rois[_normalize]).
+# An added export alone does not bump it (vacv_crop_resize_rois[_normalize],
+# vacv_cvt_color_crop_resize_rois[_normalize]).
 ABI_VERSION = 5
 
 _lib = None

@@ -525,6 +525,46 @@ def cvt_color_warp_affine_rois_normalize(yuv: torch.Tensor, ms, w: int, h: int, 
     return out
 
 
+def cvt_color_crop_resize_rois(yuv: torch.Tensor, rects, w: int, h: int, code: int = L.COLOR_YUV2BGR_NV21,
+                               src_index=None, mode: int = LINEAR_REFERENCE, out=None,
+                               stream=None) -> torch.Tensor:
+    """Many upright crops straight from NV21 / NV12 frames in one launch:
+    out[i] = resize(crop(cvt_color(yuv[src_index[i]], code), rects[i]), w, h),
+    byte for byte, without the decoded frames or the crops.  yuv:
+    (n, h_in*3/2, w_in) u8 frames or one (h_in*3/2, w_in) frame; rects: (n, 4)
+    int32 device tensor of (left, top, width, height) in the decoded frame;
+    src_index as crop_resize_rois takes it.  Both are read by the kernel when
+    it runs on `stream`; an invalid rect or index gives a ROI of zeros.
+    Returns (n, h, w, 3) u8."""
+    y4 = _yuv4(yuv)
+    _, rects, src_index, n = _roi_batch(_as4d(y4.unsqueeze(-1), NHWC), rects, *_RECTS, src_index)
+    if out is None:
+        out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=yuv.device)
+    check("vacv_cvt_color_crop_resize_rois", L.load().vacv_cvt_color_crop_resize_rois(
+        ctypes.byref(_yuv_desc(y4)), ctypes.byref(describe(out, NHWC)), code, rects.data_ptr(),
+        _idx_ptr(src_index), INTER_LINEAR, mode, _stream(stream)))
+    return out
+
+
+def cvt_color_crop_resize_rois_normalize(yuv: torch.Tensor, rects, w: int, h: int, mean, std,
+                                         code: int = L.COLOR_YUV2BGR_NV21, src_index=None,
+                                         mode: int = LINEAR_REFERENCE, layout: int = NHWC, out=None,
+                                         stream=None) -> torch.Tensor:
+    """cvt_color_crop_resize_rois with the fused normalize: fp32 (n, h, w, 3),
+    or planar (n, 3, h, w) with layout=NCHW, the model-input layout."""
+    y4 = _yuv4(yuv)
+    _, rects, src_index, n = _roi_batch(_as4d(y4.unsqueeze(-1), NHWC), rects, *_RECTS, src_index)
+    if mean is None or std is None:
+        raise ValueError("cvt_color_crop_resize_rois_normalize needs mean and stddev (no per-image statistics for ROIs)")
+    if out is None:
+        out = torch.empty((n, h, w, 3) if layout == NHWC else (n, 3, h, w), dtype=torch.float32, device=yuv.device)
+    (ma, meanp), (sa, stdp) = _meanstd(mean, std, 3)
+    check("vacv_cvt_color_crop_resize_rois_normalize", L.load().vacv_cvt_color_crop_resize_rois_normalize(
+        ctypes.byref(_yuv_desc(y4)), ctypes.byref(describe(out, layout)), code, rects.data_ptr(),
+        _idx_ptr(src_index), INTER_LINEAR, mode, meanp, stdp, _stream(stream)))
+    return out
+
+
 # ---------------------------------------------------------------------------
 # normalize / statistics
 

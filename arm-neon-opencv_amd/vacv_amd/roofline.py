@@ -191,3 +191,23 @@ def crop_resize_rois_bytes(c: int, in_esize: int, w_out: int, h_out: int, rects,
             continue
         total += w * h * c * in_esize
     return int(total)
+
+
+def yuv_crop_resize_rois_bytes(w_out: int, h_out: int, rects, out_esize: int = 1, w_in: int = None,
+                               h_in: int = None) -> int:
+    """B_alg of vacv_cvt_color_crop_resize_rois[_normalize]: the 3-channel
+    output bytes of every ROI plus, per valid rect (judged as
+    crop_resize_rois_bytes judges it, in the decoded w_in x h_in frame), its
+    w * h Y bytes and the chroma pairs that cover it -- columns left >> 1 to
+    (left + w - 1) >> 1 of chroma rows top >> 1 to (top + h - 1) >> 1, 2 bytes
+    each.  An invalid rect reads nothing and counts its output only."""
+    r = np.asarray(rects, dtype=np.int64).reshape(-1, 4)
+    total = r.shape[0] * w_out * h_out * 3 * out_esize
+    for left, top, w, h in r.tolist():
+        if w < 2 or h < 2 or left < 0 or top < 0:
+            continue
+        if (w_in is not None and left + w > w_in) or (h_in is not None and top + h > h_in):
+            continue
+        total += w * h
+        total += 2 * (((left + w - 1) >> 1) - (left >> 1) + 1) * (((top + h - 1) >> 1) - (top >> 1) + 1)
+    return int(total)

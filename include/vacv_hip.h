@@ -426,6 +426,39 @@ int vacv_cvt_color_warp_affine_rois_normalize(const vacv_image* src, const vacv_
                                     const double border_value[4],
                                     const float* mean, const float* stddev, void* stream);
 
+/* The same second stage for upright boxes: many crop + resize ROIs straight
+ * from NV21 / NV12 frames in one launch, without the decoded frames and
+ * without the crops.
+ * src, code: exactly as vacv_cvt_color_warp_affine_rois.
+ * dst: `dst->n` ROIs of dst->w x dst->h, c = 3.
+ *      vacv_cvt_color_crop_resize_rois:           INT8 NHWC, dense or pitched
+ *      vacv_cvt_color_crop_resize_rois_normalize: FP32, NHWC or NCHW, dense or
+ *        pitched (row, plane and batch pitch); mean / stddev: host arrays of 3
+ *        floats, both required (one NULL: INVALID_ARG; both NULL: UNSUPPORTED).
+ * rects, src_index, interpolation, mode: exactly as vacv_crop_resize_rois
+ * (DEVICE arrays read by the kernel at execution time, never dereferenced by
+ * the host; the same NULL-index rules; INTER_LINEAR only; mode
+ * VACV_LINEAR_REFERENCE / _NEON / _OPENCV).  A rect is (left, top, width,
+ * height) in the DECODED w x h frame.
+ * ROI i is byte-identical to vacv_cvt_color(frame src_index[i], code)
+ * followed by vacv_crop_resize_rois[_normalize] on that decoded (w, h, 3)
+ * frame with rects[i]; bytes of the dst allocation outside the ROI rectangles
+ * are never written.  The call copies nothing between host and device,
+ * allocates nothing and never synchronizes.  Device-supplied values cannot
+ * fault: an index outside [0, src->n), a width or height below 2, a negative
+ * origin or an edge past the decoded frame gives a ROI of zeros (normalize:
+ * the normalized value of 0) and reads nothing; every source read is
+ * range-checked by the hardware against the indexed frame's Y and chroma
+ * rows.  A destination wider than 2^20 pixels or a frame of 2 GiB or more:
+ * UNSUPPORTED. */
+int vacv_cvt_color_crop_resize_rois(const vacv_image* src, const vacv_image* dst, int code,
+                                    const int32_t* rects, const int32_t* src_index,
+                                    int interpolation, int mode, void* stream);
+int vacv_cvt_color_crop_resize_rois_normalize(const vacv_image* src, const vacv_image* dst, int code,
+                                    const int32_t* rects, const int32_t* src_index,
+                                    int interpolation, int mode,
+                                    const float* mean, const float* stddev, void* stream);
+
 /* ---- template matching ------------------------------------------------ */
 
 /* va_cv::VMatchMode (cv.h:52-59) */

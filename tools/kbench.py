@@ -29,7 +29,9 @@ def main():
                     help="--op warp_rois: time each one-call case against the same crops as a loop of single "
                          "calls (vacv_warp_affine; vacv_warp_affine_normalize + one vacv_change_layout), alternating; "
                          "--op yuv_rois: against vacv_cvt_color of all frames + vacv_warp_affine_rois[_normalize]; "
-                         "--op crop_resize_rois: against a loop of vacv_crop + vacv_resize[_normalize] single calls")
+                         "--op crop_resize_rois: against a loop of vacv_crop + vacv_resize[_normalize] single calls; "
+                         "--op yuv_crop_resize_rois: against vacv_cvt_color of all frames + "
+                         "vacv_crop_resize_rois[_normalize]")
     ap.add_argument("--baseline-lib", default="",
                     help="--compare: libvacv_hip.so of another build (e.g. the parent commit's) to run the loop on; "
                          "default: this build's own single-call entry points")
@@ -311,8 +313,53 @@ def main():
             crop_resize_rois_bytes(3, 1, 140, 210, rects7, 1), 64 * 140 * 210)
         crop_loops["crop_resize_rois_720p_64x140x210_u8"] = dict(src=src7, rects=rects7, idx=np.zeros(64, np.int32),
                                                                  out=torch.empty_like(o7), norm=False)
+    crop_chains = {}
+    if a.op in ("yuv_crop_resize_rois", "all"):
+        # the crop_resize_rois cases with NV21 frames as the source
+        # (vacv_cvt_color_crop_resize_rois): the same seeded boxes
+        import numpy as np
+        from vacv_amd.roofline import yuv_crop_resize_rois_bytes
+        rng = np.random.default_rng(20261020)
+
+        def yuv_roi_rects(n, fw, fh, lo=32, hi=400):
+            wh = rng.integers(lo, hi + 1, (n, 2))
+            lt = (rng.random((n, 2)) * (np.array([fw, fh]) - wh + 1)).astype(np.int64)
+            return np.concatenate([lt, wh], 1).astype(np.int32)
+
+        yuv = torch.randint(0, 256, (8, 1620, 1920), dtype=torch.uint8, device=dev, generator=g)
+        rects = yuv_roi_rects(256, 1920, 1080)
+        idx = np.arange(256, dtype=np.int32) % 8
+        drects, didx = torch.from_numpy(rects).to(dev), torch.from_numpy(idx).to(dev)
+        o = torch.empty((256, 112, 112, 3), dtype=torch.uint8, device=dev)
+        cases["yuv_crop_resize_rois_1080p_256x112_u8"] = (
+            lambda yuv=yuv, drects=drects, didx=didx, o=o: ops.cvt_color_crop_resize_rois(yuv, drects, 112, 112,
+                                                                                         src_index=didx, out=o),
+            yuv_crop_resize_rois_bytes(112, 112, rects, 1, 1920, 1080), 256 * 112 * 112)
+        crop_chains["yuv_crop_resize_rois_1080p_256x112_u8"] = dict(yuv=yuv, rects=drects, idx=didx,
+                                                                    out=torch.empty_like(o), norm=False)
+        of = torch.empty((256, 3, 112, 112), dtype=torch.float32, device=dev)
+        cases["yuv_crop_resize_rois_normalize_1080p_256x112_chw"] = (
+            lambda yuv=yuv, drects=drects, didx=didx, of=of: ops.cvt_color_crop_resize_rois_normalize(
+                yuv, drects, 112, 112, MEAN, STD, src_index=didx, layout=vacv_amd.NCHW, out=of),
+            yuv_crop_resize_rois_bytes(112, 112, rects, 4, 1920, 1080), 256 * 112 * 112)
+        crop_chains["yuv_crop_resize_rois_normalize_1080p_256x112_chw"] = dict(yuv=yuv, rects=drects, idx=didx,
+                                                                               out=torch.empty_like(of), norm=True)
+        # the reference harness's crop size: 64 crops of one 1280 x 720 frame
+        yuv7 = torch.randint(0, 256, (1, 1080, 1280), dtype=torch.uint8, device=dev, generator=g)
+        rects7 = yuv_roi_rects(64, 1280, 720)
+        drects7 = torch.from_numpy(rects7).to(dev)
+        o7 = torch.empty((64, 210, 140, 3), dtype=torch.uint8, device=dev)
+        cases["yuv_crop_resize_rois_720p_64x140x210_u8"] = (
+            lambda yuv7=yuv7, drects7=drects7, o7=o7: ops.cvt_color_crop_resize_rois(yuv7, drects7, 140, 210, out=o7),
+            yuv_crop_resize_rois_bytes(140, 210, rects7, 1, 1280, 720), 64 * 140 * 210)
+        crop_chains["yuv_crop_resize_rois_720p_64x140x210_u8"] = dict(yuv=yuv7, rects=drects7, idx=None,
+                                                                      out=torch.empty_like(o7), norm=False)
     if a.only:
         cases = {k: v for k, v in cases.items() if a.only in k}
+    if a.compare and a.op == "yuv_crop_resize_rois":
+        compare_with_crop_chains({k: v for k, v in cases.items() if k in crop_chains}, crop_chains, a.baseline_lib,
+                                 a.iters)
+        return
     if a.compare and a.op == "crop_resize_rois":
         compare_with_crop_loops({k: v for k, v in cases.items() if k in crop_loops}, crop_loops, a.iters)
         return
@@ -485,6 +532,93 @@ def compare_with_chains(cases, chains, baseline_lib, iters):
                           "one_call_ms_median": round(mo, 4), "one_call_ms_min": round(t_one[0], 4),
                           "one_call_ms_p90": round(t_one[iters * 9 // 10], 4),
                           "chain_over_one_call": round(mc / mo, 2), "alg_bytes": int(nbytes),
+                          "one_call_alg_GBps": round(nbytes / mo / 1e6, 1), "outputs_equal": same,
+                          "clock": "host, stream synchronised"}), flush=True)
+
+
+def compare_with_crop_chains(cases, chains, baseline_lib, iters):
+    """--op yuv_crop_resize_rois: the one call against the chain it replaces --
+    vacv_cvt_color of all frames into a preallocated BGR buffer, then
+    vacv_crop_resize_rois[_normalize] on it -- per case, both timed end to end
+    with a host clock around a synchronised stream, alternating, after warm-up;
+    medians with p10-p90, outputs compared equal.  The chain runs on
+    `baseline_lib` (e.g. the parent commit's build) by its own handle, or on
+    this build.  Both legs are ctypes calls whose descriptors were built
+    beforehand, so what is timed is the library."""
+    import ctypes
+    import time
+
+    import torch
+    import vacv_amd
+    from vacv_amd import _lib as L, ops
+    lib = L.load()
+    if baseline_lib:
+        base = ctypes.CDLL(str(Path(baseline_lib).resolve()))
+        for fname in ("vacv_cvt_color", "vacv_crop_resize_rois", "vacv_crop_resize_rois_normalize", "vacv_abi_version"):
+            getattr(base, fname).argtypes, getattr(base, fname).restype = L.SIGNATURES[fname]
+        tag = f"{baseline_lib} (ABI {base.vacv_abi_version()})"
+    else:
+        base, tag = lib, "this build"
+    stream = ops._stream()
+    mean, std = (ctypes.c_float * 3)(*MEAN), (ctypes.c_float * 3)(*STD)
+    code, linear, ref = L.COLOR_YUV2BGR_NV21, vacv_amd.INTER_LINEAR, vacv_amd.LINEAR_REFERENCE
+    for name, (binding_call, nbytes, px) in cases.items():
+        ch = chains[name]
+        yuv, rects, idx, out, norm = ch["yuv"], ch["rects"], ch["idx"], ch["out"], ch["norm"]
+        bgr = torch.empty((yuv.shape[0], yuv.shape[1] // 3 * 2, yuv.shape[2], 3), dtype=torch.uint8, device=yuv.device)
+        yd, bd = ops._yuv_desc(yuv), ops.describe(bgr)
+        od = ops.describe(out, vacv_amd.NCHW if norm else vacv_amd.NHWC)
+        rp, ip = rects.data_ptr(), (idx.data_ptr() if idx is not None else None)
+
+        def chain():
+            assert base.vacv_cvt_color(ctypes.byref(yd), ctypes.byref(bd), code, stream) == 0
+            if norm:
+                assert base.vacv_crop_resize_rois_normalize(ctypes.byref(bd), ctypes.byref(od), rp, ip, linear, ref, mean,
+                                                            std, stream) == 0
+            else:
+                assert base.vacv_crop_resize_rois(ctypes.byref(bd), ctypes.byref(od), rp, ip, linear, ref, stream) == 0
+
+        one = binding_call()  # the binding's own output tensor, written by the calls below
+        od1 = ops.describe(one, vacv_amd.NCHW if norm else vacv_amd.NHWC)
+
+        def fn():
+            if norm:
+                assert lib.vacv_cvt_color_crop_resize_rois_normalize(ctypes.byref(yd), ctypes.byref(od1), code, rp, ip,
+                                                                     linear, ref, mean, std, stream) == 0
+            else:
+                assert lib.vacv_cvt_color_crop_resize_rois(ctypes.byref(yd), ctypes.byref(od1), code, rp, ip, linear, ref,
+                                                           stream) == 0
+
+        def timed(f):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            f()
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) * 1e3
+
+        one.zero_()
+        for _ in range(20):
+            chain()
+            fn()
+        torch.cuda.synchronize()
+        same = bool(torch.equal(one, out))  # both legs compute the same crops
+        t_chain, t_one = [], []
+        for _ in range(iters):
+            t_chain.append(timed(chain))
+            t_one.append(timed(fn))
+        t_chain.sort()
+        t_one.sort()
+        mc, mo = t_chain[iters // 2], t_one[iters // 2]
+        c10, c90 = t_chain[iters // 10], t_chain[iters * 9 // 10]
+        print(json.dumps({"case": name, "rois": int(rects.shape[0]), "frames": int(yuv.shape[0]), "baseline": tag,
+                          "iters": iters, "chain_ms_median": round(mc, 4), "chain_ms_min": round(t_chain[0], 4),
+                          "chain_ms_p10": round(c10, 4), "chain_ms_p90": round(c90, 4),
+                          "chain_p10_p90_half_width_ms": round((c90 - c10) / 2, 4),
+                          "one_call_ms_median": round(mo, 4), "one_call_ms_min": round(t_one[0], 4),
+                          "one_call_ms_p10": round(t_one[iters // 10], 4),
+                          "one_call_ms_p90": round(t_one[iters * 9 // 10], 4),
+                          "chain_over_one_call": round(mc / mo, 2),
+                          "one_call_within_chain_noise": bool(mo <= mc + (c90 - c10) / 2), "alg_bytes": int(nbytes),
                           "one_call_alg_GBps": round(nbytes / mo / 1e6, 1), "outputs_equal": same,
                           "clock": "host, stream synchronised"}), flush=True)
 
