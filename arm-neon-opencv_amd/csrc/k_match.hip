@@ -294,10 +294,13 @@ __global__ void __launch_bounds__(kBlock) match_integral_cols_kernel(MatchLaunch
 }
 
 // one output: S_c / Q from the integral images (templmatch.cpp's p0 - p1 -
-// p2 + p3), then its normalisation formula, in its operation order
+// p2 + p3), then its normalisation formula, in its operation order.  Grid
+// (ceil(rw / kBlock) * rh, 1, n): the result row is folded into x, since rh
+// may pass the 65,535 blocks of a grid's y (host-checked: the product fits int)
 __global__ void __launch_bounds__(kBlock) match_finish_kernel(MatchLaunch M) {
-    const int x = blockIdx.x * kBlock + threadIdx.x;
-    const int r = blockIdx.y, img = blockIdx.z;
+    const int bx = (M.rw + kBlock - 1) / kBlock;  // workgroups per result row
+    const int r = (int)blockIdx.x / bx, img = blockIdx.z;
+    const int x = ((int)blockIdx.x - r * bx) * kBlock + threadIdx.x;
     if (x >= M.rw) return;
     const int cn = M.cn;
     const int64_t step = (int64_t)(M.iw + 1) * cn;
@@ -909,7 +912,7 @@ hipError_t launch_match_template(const MatchLaunch& M, hipStream_t s) {
     }
     const dim3 gc((2 * (M.iw + 1) * M.cn + kBlock - 1) / kBlock, M.n);
     hipLaunchKernelGGL(match_integral_cols_kernel, gc, dim3(kBlock), 0, s, M);
-    const dim3 gf((M.rw + kBlock - 1) / kBlock, M.rh, M.n);
+    const dim3 gf((unsigned)((M.rw + kBlock - 1) / kBlock) * (unsigned)M.rh, 1, M.n);
     hipLaunchKernelGGL(match_finish_kernel, gf, dim3(kBlock), 0, s, M);
     return hipGetLastError();
 }

@@ -1243,6 +1243,8 @@ int vacv_match_template(const vacv_image* img_d, const vacv_image* tpl_d, const 
         return VACV_ERR_INVALID_ARG;
     if (match_lds_bytes(tpl.w, tpl.h, img.c, img.es) > 64 * 1024 || rh > 65535 * 4 || img.n > 65535)
         return VACV_ERR_UNSUPPORTED;
+    // match_finish_kernel's grid x: a workgroup per 256 result columns of every result row
+    if ((int64_t)((rw + 255) / 256) * rh > INT32_MAX) return VACV_ERR_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
     MatchLaunch M{};
     M.img = img.data;

@@ -662,8 +662,13 @@ def match_template(img: torch.Tensor, templ: torch.Tensor, method: int, out=None
     t4 = _as4d(templ, NHWC)
     n, H, W, _ = i4.shape
     _, h, w, _ = t4.shape
-    if w > W and h > H and n == 1:
+    # vacv_match_template's (cv::matchTemplate's) rule: a template at least as
+    # large as the image in both directions, and larger in one, is the image
+    if w >= W and h >= H and (w > W or h > H) and n == 1:
         W, H, w, h = w, h, W, H
+    if w > W or h > H:
+        raise ValueError(f"match_template: a {w} x {h} template does not fit the {W} x {H} image"
+                         + (" (a batch is never swapped)" if n > 1 else ""))
     if out is None:
         out = torch.empty((n, H - h + 1, W - w + 1), dtype=torch.float32, device=img.device)
     o4 = out.reshape(n, H - h + 1, W - w + 1, 1)  # one channel, NHWC

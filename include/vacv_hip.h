@@ -472,9 +472,12 @@ enum {
  * with the correlation computed exactly (parity unpinned).
  * img: n images (W, H, c) NHWC INT8 or FP32, c <= 4; templ: (w, h, c), same
  * dtype, n = 1, shared by every image; result: n x (W-w+1, H-h+1, 1) FP32.
- * A template larger than the image in both dimensions swaps the two, as
- * cv::matchTemplate does.  VACV_ERR_UNSUPPORTED when the template does not
- * fit the kernel's LDS budget (about 64 KiB of template bytes). */
+ * A template at least as large as the image in both dimensions and larger
+ * in one (w >= W && h >= H && (w > W || h > H)) swaps the two, as
+ * cv::matchTemplate does (n = 1 only).  VACV_ERR_UNSUPPORTED, with nothing
+ * written, when the template does not fit the kernel's LDS budget (about
+ * 64 KiB of template bytes), for more than 65535 * 4 result rows, or when
+ * ceil((W-w+1) / 256) * (H-h+1) does not fit an int. */
 int vacv_match_template(const vacv_image* img, const vacv_image* templ, const vacv_image* result, int method,
                         void* stream);
 

@@ -37,6 +37,8 @@ EXPORTS = [
     "va_cv::warp_affine_normalize(vision::Tensor const&, vision::Tensor&, float, float, va_cv::VSize, "
     "va_cv::VScalar const&, int, int, va_cv::VScalar const&, vision::Tensor const&, vision::Tensor const&)",
     "va_cv::crop(vision::Tensor const&, vision::Tensor&, vision::VRect const&)",
+    "va_cv::match_template(vision::Tensor const&, vision::Tensor const&, vision::Tensor&, int)",
+    "va_cv::minMaxIdx(vision::Tensor const&, double*, double*, int*, int*, vision::Tensor const&)",
     "vision::Tensor::change_layout(vision::DLayout)",
     "vision::Tensor::change_dtype(vision::DType)",
     "vision::Tensor::clone() const",
