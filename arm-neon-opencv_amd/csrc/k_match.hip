@@ -27,6 +27,7 @@
 
 #include <algorithm>
 
+#include "match_formula.hpp"
 #include "vacv_device.hpp"
 
 namespace vacv {
@@ -308,46 +309,12 @@ __global__ void __launch_bounds__(kBlock) match_finish_kernel(MatchLaunch M) {
     const double* sq = sum + (int64_t)(M.ih + 1) * step;
     const double* ts = M.tstats;  // tmean[4], templNorm, templSum2, all-ones flag
     float* out = reinterpret_cast<float*>(M.res + (int64_t)img * M.res_pitch + (int64_t)r * M.res_row) + x;
-    const int method = M.method;
-    if (ts[6] != 0.0) {  // CCOEFF_NORMED of a flat template
-        *out = 1.f;
-        return;
-    }
     const int64_t i0 = (int64_t)r * step + (int64_t)x * cn;
     const int64_t dw = (int64_t)M.tw * cn, dh = (int64_t)M.th * step;
-    const int numType = (method == VACV_TM_CCORR || method == VACV_TM_CCORR_NORMED)     ? 0
-                        : (method == VACV_TM_CCOEFF || method == VACV_TM_CCOEFF_NORMED) ? 1
-                                                                                        : 2;
-    const bool isNormed = method == VACV_TM_CCORR_NORMED || method == VACV_TM_SQDIFF_NORMED ||
-                          method == VACV_TM_CCOEFF_NORMED;
-    const double invArea = M.inv_area;
-    double num = (double)*out, t;
-    double wndMean2 = 0, wndSum2 = 0;
-    if (numType == 1) {
-        for (int c = 0; c < cn; ++c) {
-            t = sum[i0 + c] - sum[i0 + dw + c] - sum[i0 + dh + c] + sum[i0 + dh + dw + c];
-            wndMean2 += t * t;
-            num -= t * ts[c];
-        }
-        wndMean2 *= invArea;
-    }
-    if (isNormed || numType == 2) {
-        for (int c = 0; c < cn; ++c) {
-            t = sq[i0 + c] - sq[i0 + dw + c] - sq[i0 + dh + c] + sq[i0 + dh + dw + c];
-            wndSum2 += t;
-        }
-        if (numType == 2) {
-            num = wndSum2 - 2 * num + ts[5];
-            num = num > 0. ? num : 0.;
-        }
-    }
-    if (isNormed) {
-        t = sqrt(wndSum2 - wndMean2 > 0. ? wndSum2 - wndMean2 : 0.) * ts[4];
-        if (fabs(num) < t) num /= t;
-        else if (fabs(num) < t * 1.125) num = num > 0 ? 1 : -1;
-        else num = method != VACV_TM_SQDIFF_NORMED ? 0 : 1;
-    }
-    *out = (float)num;
+    *out = match_normalise(
+        *out, cn, M.method, ts, M.inv_area,
+        [&](int c) { return sum[i0 + c] - sum[i0 + dw + c] - sum[i0 + dh + c] + sum[i0 + dh + dw + c]; },
+        [&](int c) { return sq[i0 + c] - sq[i0 + dw + c] - sq[i0 + dh + c] + sq[i0 + dh + dw + c]; });
 }
 
 // ---- u8 window statistics: exact integer box sums (round 6) -----------------
@@ -487,49 +454,13 @@ __global__ void __launch_bounds__(kBlock) match_finish_u8_kernel(MatchLaunch M) 
     __syncthreads();
     // the result row: match_finish_kernel's formula with the window sums
     const double* tsd = M.tstats;  // tmean[4], templNorm, templSum2, all-ones flag
-    const int method = M.method;
-    const int numType = (method == VACV_TM_CCORR || method == VACV_TM_CCORR_NORMED)     ? 0
-                        : (method == VACV_TM_CCOEFF || method == VACV_TM_CCOEFF_NORMED) ? 1
-                                                                                        : 2;
-    const bool isNormed = method == VACV_TM_CCORR_NORMED || method == VACV_TM_SQDIFF_NORMED ||
-                          method == VACV_TM_CCOEFF_NORMED;
-    const double invArea = M.inv_area;
     const int dw = M.tw * cn;
     float* orow = reinterpret_cast<float*>(M.res + (int64_t)img * M.res_pitch + (int64_t)r * M.res_row);
     for (int x = tid; x < M.rw; x += kBlock) {
-        float* out = orow + x;
-        if (tsd[6] != 0.0) {  // CCOEFF_NORMED of a flat template
-            *out = 1.f;
-            continue;
-        }
         const int i0 = x * cn;
-        double num = (double)*out, t;
-        double wndMean2 = 0, wndSum2 = 0;
-        if (numType == 1) {
-            for (int c = 0; c < cn; ++c) {
-                t = (double)(ps[i0 + dw + c] - ps[i0 + c]);
-                wndMean2 += t * t;
-                num -= t * tsd[c];
-            }
-            wndMean2 *= invArea;
-        }
-        if (isNormed || numType == 2) {
-            for (int c = 0; c < cn; ++c) {
-                t = (double)(pq[i0 + dw + c] - pq[i0 + c]);
-                wndSum2 += t;
-            }
-            if (numType == 2) {
-                num = wndSum2 - 2 * num + tsd[5];
-                num = num > 0. ? num : 0.;
-            }
-        }
-        if (isNormed) {
-            t = sqrt(wndSum2 - wndMean2 > 0. ? wndSum2 - wndMean2 : 0.) * tsd[4];
-            if (fabs(num) < t) num /= t;
-            else if (fabs(num) < t * 1.125) num = num > 0 ? 1 : -1;
-            else num = method != VACV_TM_SQDIFF_NORMED ? 0 : 1;
-        }
-        *out = (float)num;
+        orow[x] = match_normalise(
+            orow[x], cn, M.method, tsd, M.inv_area, [&](int c) { return (double)(ps[i0 + dw + c] - ps[i0 + c]); },
+            [&](int c) { return (double)(pq[i0 + dw + c] - pq[i0 + c]); });
     }
 }
 
@@ -564,34 +495,11 @@ __global__ void __launch_bounds__(kBlock) match_tstats_kernel(MatchLaunch M) {
         __syncthreads();
     }
     if (threadIdx.x != 0) return;
-    double tm[4] = {0, 0, 0, 0}, td[4] = {0, 0, 0, 0};
-    for (int c = 0; c < cn; ++c) {  // meanStdDev: population
-        tm[c] = red[0][c][0] / n;
-        const double var = red[1][c][0] / n - tm[c] * tm[c];
-        td[c] = sqrt(var > 0 ? var : 0);
-    }
-    const int method = M.method;
-    const double invArea = M.inv_area;
-    double templNorm = 0, templSum2 = 0, ones = 0;
-    double tmean[4] = {tm[0], tm[1], tm[2], tm[3]};
-    if (method != VACV_TM_CCOEFF) {
-        templNorm = td[0] * td[0] + td[1] * td[1] + td[2] * td[2] + td[3] * td[3];
-        if (templNorm < 2.220446049250313e-16 && method == VACV_TM_CCOEFF_NORMED) ones = 1;
-        templSum2 = templNorm + tm[0] * tm[0] + tm[1] * tm[1] + tm[2] * tm[2] + tm[3] * tm[3];
-        const bool ccoeff = method == VACV_TM_CCOEFF || method == VACV_TM_CCOEFF_NORMED;
-        if (!ccoeff) {
-            tmean[0] = tmean[1] = tmean[2] = tmean[3] = 0;
-            templNorm = templSum2;
-        }
-        templSum2 /= invArea;
-        templNorm = sqrt(templNorm);
-        templNorm /= sqrt(invArea);
-    }
-    double* o = M.tstats;
-    for (int c = 0; c < 4; ++c) o[c] = tmean[c];
-    o[4] = templNorm;
-    o[5] = templSum2;
-    o[6] = ones;
+    const double ts[4] = {red[0][0][0], red[0][1][0], red[0][2][0], red[0][3][0]};
+    const double tq[4] = {red[1][0][0], red[1][1][0], red[1][2][0], red[1][3][0]};
+    double o[7];
+    match_template_consts(ts, tq, cn, n, M.method, M.inv_area, o);
+    for (int k = 0; k < 7; ++k) M.tstats[k] = o[k];
 }
 
 // ---- minMaxIdx ---------------------------------------------------------------

@@ -1284,6 +1284,56 @@ int vacv_match_template(const vacv_image* img_d, const vacv_image* tpl_d, const 
     return hip_status(launch_match_template(M, s));
 }
 
+// ROI i = vacv_match_template of the window at origin[i] of frame src_index[i]
+// against template i, and its vacv_min_max_idx (k_match_rois.hip).  origin,
+// src_index, vals and idx are device arrays: validated for presence only,
+// never read here.  The order: descriptors, origin, what the kernel does not
+// compute (UNSUPPORTED), shapes that contradict each other (INVALID_ARG), the
+// host-known limits (UNSUPPORTED), then how the optional arrays pair up.
+int vacv_match_template_rois(const vacv_image* src_d, const vacv_image* tpl_d, const vacv_image* res_d,
+                             const int32_t* origin, const int32_t* src_index, int method, double* vals,
+                             int32_t* idx, void* stream) {
+    Img src, tpl, res;
+    int st = load(src_d, src);
+    if (st) return st;
+    if ((st = load(tpl_d, tpl))) return st;
+    if ((st = load(res_d, res))) return st;
+    if (!origin) return VACV_ERR_INVALID_ARG;
+    if (method < VACV_TM_SQDIFF || method > VACV_TM_CCOEFF_NORMED) return VACV_ERR_UNSUPPORTED;
+    if (src.dtype != VACV_INT8) return VACV_ERR_UNSUPPORTED;  // FP32: order-dependent double sums, not built
+    if (src.layout != VACV_NHWC || tpl.layout != VACV_NHWC || src.c > 4) return VACV_ERR_UNSUPPORTED;
+    if (tpl.dtype != src.dtype || tpl.c != src.c) return VACV_ERR_INVALID_ARG;
+    if (tpl.n != 1 && tpl.n != res.n) return VACV_ERR_INVALID_ARG;
+    if (res.dtype != VACV_FP32 || res.c != 1) return VACV_ERR_INVALID_ARG;
+    // the uint32 window sums' bound, as launch_match_template's u8 path
+    if ((int64_t)tpl.w * tpl.h > 66000) return VACV_ERR_UNSUPPORTED;
+    if (match_rois_lds_bytes(tpl.w, tpl.h, src.c, res.w, res.h) > 64 * 1024) return VACV_ERR_UNSUPPORTED;
+    if (res.n > (int)(UINT32_MAX / kBlock)) return VACV_ERR_UNSUPPORTED;  // a workgroup per ROI: the grid's threads fit 32 bits
+    if (!vals != !idx) return VACV_ERR_INVALID_ARG;
+    if (!roi_frames_ok(src, res, src_index)) return VACV_ERR_INVALID_ARG;
+    MatchRoisLaunch M{};
+    M.src = geom(src);
+    M.n_src = src.n;
+    M.n_roi = res.n;
+    M.tpl = tpl.data;
+    M.tpl_pitch = tpl.n == 1 ? 0 : tpl.batch;
+    M.tpl_row = tpl.row;
+    M.tw = tpl.w;
+    M.th = tpl.h;
+    M.res = res.data;
+    M.res_pitch = res.batch;
+    M.res_row = res.row;
+    M.rw = res.w;
+    M.rh = res.h;
+    M.origin = origin;
+    M.src_index = src_index;
+    M.method = method;
+    M.inv_area = 1. / ((double)tpl.h * tpl.w);
+    M.vals = vals;
+    M.idx = idx;
+    return hip_status(launch_match_rois(M, (hipStream_t)stream));
+}
+
 int vacv_min_max_idx(const vacv_image* src_d, const vacv_image* mask_d, double* vals, int* idx, void* stream) {
     Img src, mask;
     int st = load(src_d, src);

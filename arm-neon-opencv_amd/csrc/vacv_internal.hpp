@@ -426,6 +426,29 @@ bool match_mfma_plan(int tw, int th, int cn, int& KB, int& stride);
 size_t match_bfrag_bytes(int tw, int th, int cn);
 hipError_t launch_match_template(const MatchLaunch& M, hipStream_t s);
 
+// Many matches in one launch (k_match_rois.hip): ROI i = match_template of the
+// (rw + tw - 1) x (rh + th - 1) window at origin[i] of frame src_index[i]
+// against template i, and its minMaxIdx; the arrays are device memory read by
+// the kernel.  u8 only.
+struct MatchRoisLaunch {
+    PlaneGeom src;                // NHWC u8 frames (planes = 1)
+    int n_src, n_roi;
+    const unsigned char* tpl;     // template 0
+    int64_t tpl_pitch, tpl_row;   // bytes; tpl_pitch 0: one template for every ROI
+    int tw, th;
+    unsigned char* res;           // FP32 result of ROI 0
+    int64_t res_pitch, res_row;   // bytes
+    int rw, rh;
+    const int32_t* origin;        // device [n_roi][2]: left, top of the search window
+    const int32_t* src_index;     // device [n_roi], or null: frame 0 (n_src == 1) or frame i
+    int method;                   // VACV_TM_*
+    double inv_area;              // 1 / (tw * th)
+    double* vals;                 // device [n_roi][2]: min, max; or null (with idx): no peaks
+    int32_t* idx;                 // device [n_roi][4]: min row, min col, max row, max col
+};
+size_t match_rois_lds_bytes(int tw, int th, int cn, int rw, int rh);  // a workgroup's LDS (the host refuses > 64 KiB)
+hipError_t launch_match_rois(const MatchRoisLaunch& M, hipStream_t s);
+
 struct MinMaxLaunch {             // minMaxIdx of one single-channel image
     const unsigned char* src;
     int64_t row;

@@ -372,6 +372,7 @@ struct RoiStage {
     Tensor pinned;  // the per-crop parameters on the host
     bool queued = false;
     unsigned char* crops = nullptr;
+    unsigned char* tail_ptr = nullptr;
     size_t roi_bytes = 0;
 
     RoiStage(const char* fn_, const Tensor& src) : fn(fn_), lease(detail::compute_device(src)), s(lease.stream()) {}
@@ -401,10 +402,12 @@ struct RoiStage {
         }
         return detail::describe(src, d);
     }
-    // n crops back to back: scratch slot 2
-    vacv_image out(size_t n, VSize size, int c, DType dtype) {
+    // n crops back to back: scratch slot 2; `tail` more bytes behind them (16-byte aligned) at tail_ptr
+    vacv_image out(size_t n, VSize size, int c, DType dtype, size_t tail = 0) {
         roi_bytes = (size_t)size.w * size.h * c * dtype_size(dtype);
-        crops = static_cast<unsigned char*>(lease.scratch(2, n * roi_bytes));
+        const size_t body = (n * roi_bytes + 15) / 16 * 16;
+        crops = static_cast<unsigned char*>(lease.scratch(2, body + tail));
+        tail_ptr = crops + body;
         return vacv_image{crops, (int)n, size.w, size.h, c, dtype, NHWC, 0, 0, 0};  // pitches 0 = dense
     }
     // every crop into a tensor of its own with src's placement, then wait
@@ -659,6 +662,86 @@ void minMaxIdx(const Tensor& src, double* minVal, double* maxVal, int* minIdx, i
     if (maxVal) *maxVal = hv[1];
     if (minIdx) { minIdx[0] = hi[0]; minIdx[1] = hi[1]; }
     if (maxIdx) { maxIdx[0] = hi[2]; maxIdx[1] = hi[3]; }
+}
+
+// One frame, windows.size() matches and their peaks, one launch (RoiStage):
+// the origins and the templates go to HBM in one block (host templates through
+// the pinned pool, device templates copied into their place), the kernel
+// writes the maps back to back with the peaks behind them.
+void match_template(const Tensor& src, const std::vector<Tensor>& targets, const std::vector<VRect>& windows,
+                    std::vector<Tensor>& results, int method, std::vector<VMatchPeak>* peaks) {
+    static const char* fn = "va_cv::match_template";
+    if (src.empty()) fail(fn, "empty input tensor");
+    if (src.dtype != INT8) fail(fn, "the matches of one frame take INT8");
+    if (src.layout != NHWC) fail(fn, "the matches of one frame take an NHWC frame");
+    if (windows.empty()) fail(fn, "empty window list");
+    const size_t n = windows.size();
+    if (n > 0x7FFFFFFFu) fail(fn, "too many windows");
+    if (targets.size() != 1 && targets.size() != n) fail(fn, "give one template, or one per window");
+    const Tensor& t0 = targets[0];
+    if (t0.empty()) fail(fn, "empty template");
+    for (const Tensor& t : targets) {
+        if (t.dtype != src.dtype || t.c != src.c || t.layout != NHWC)
+            fail(fn, "every template must match the frame's dtype, channels and layout");
+        if (t.w != t0.w || t.h != t0.h) fail(fn, "all templates must have one size");
+    }
+    RoiStage st(fn, src);
+    if (src.on_device() && src.device() != st.lease.device()) fail(fn, "operands live on different devices");
+    for (const Tensor& t : targets)
+        if (t.on_device() && t.device() != st.lease.device()) fail(fn, "operands live on different devices");
+
+    // [n][2] origins, then the templates, each padded to whole dwords
+    const size_t tbytes = t0.len(), tstep = (tbytes + 3) / 4 * 4, nt = targets.size();
+    int32_t* op = static_cast<int32_t*>(st.host_params(1, 2 * n + nt * (tstep / 4), "out of memory staging the windows"));
+    int ww = 0, wh = 0;
+    for (size_t i = 0; i < n; ++i) {
+        // crop.cpp:128-131
+        const int left = static_cast<int>(windows[i].left), top = static_cast<int>(windows[i].top);
+        const int cw = static_cast<int>(windows[i].width()), ch = static_cast<int>(windows[i].height());
+        if (i == 0) {
+            ww = cw;
+            wh = ch;
+        }
+        if (cw != ww || ch != wh) fail(fn, "all windows must have one size");
+        if (cw < 1 || ch < 1 || left < 0 || top < 0 || cw > src.w || left > src.w - cw || ch > src.h || top > src.h - ch)
+            fail(fn, "every window must lie inside the image");
+        op[2 * i] = left;
+        op[2 * i + 1] = top;
+    }
+    if (t0.w > ww || t0.h > wh) fail(fn, "the template does not fit the window");
+    unsigned char* tp = reinterpret_cast<unsigned char*>(op + 2 * n);
+    std::memset(tp, 0, nt * tstep);
+    for (size_t i = 0; i < nt; ++i)
+        if (!targets[i].on_device()) std::memcpy(tp + i * tstep, targets[i].data, tbytes);
+    unsigned char* dp = static_cast<unsigned char*>(st.params());
+    unsigned char* dt = dp + 2 * n * sizeof(int32_t);
+    for (size_t i = 0; i < nt; ++i)  // over the zeros of its place
+        if (targets[i].on_device())
+            detail::check_hip(fn, hipMemcpyAsync(dt + i * tstep, targets[i].data, tbytes, hipMemcpyDeviceToDevice, st.s));
+    const vacv_image sd = st.frame(src);
+    const vacv_image td{dt, (int)nt, t0.w, t0.h, t0.c, INT8, NHWC, 0, 0, (int64_t)tstep};
+    const size_t peak_bytes = peaks ? n * (2 * sizeof(double) + 4 * sizeof(int32_t)) : 0;
+    const vacv_image rd = st.out(n, VSize(ww - t0.w + 1, wh - t0.h + 1), 1, FP32, peak_bytes);
+    double* dv = peaks ? reinterpret_cast<double*>(st.tail_ptr) : nullptr;
+    int32_t* di = peaks ? reinterpret_cast<int32_t*>(st.tail_ptr + n * 2 * sizeof(double)) : nullptr;
+    detail::check(fn, vacv_match_template_rois(&sd, &td, &rd, reinterpret_cast<const int32_t*>(dp), nullptr, method, dv,
+                                               di, st.s));
+    std::vector<unsigned char> hp(peak_bytes);
+    if (peaks) detail::check_hip(fn, hipMemcpyAsync(hp.data(), st.tail_ptr, peak_bytes, hipMemcpyDeviceToHost, st.s));
+    st.scatter(results, rd, src);
+    if (!peaks) return;
+    peaks->resize(n);
+    const double* hv = reinterpret_cast<const double*>(hp.data());
+    const int32_t* hi = reinterpret_cast<const int32_t*>(hp.data() + n * 2 * sizeof(double));
+    for (size_t i = 0; i < n; ++i) {
+        VMatchPeak& p = (*peaks)[i];
+        p.minVal = hv[2 * i];
+        p.maxVal = hv[2 * i + 1];
+        p.minIdx[0] = hi[4 * i];
+        p.minIdx[1] = hi[4 * i + 1];
+        p.maxIdx[0] = hi[4 * i + 2];
+        p.maxIdx[1] = hi[4 * i + 3];
+    }
 }
 
 void imencode(const Tensor&, std::vector<unsigned char>&, const char*) {

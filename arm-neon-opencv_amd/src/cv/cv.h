@@ -259,6 +259,21 @@ void cvt_color_crop_resize_normalize(const vision::Tensor& yuv, std::vector<visi
                                      int interpolation = INTER_LINEAR,
                                      const vision::Tensor& mean = vision::Tensor(),
                                      const vision::Tensor& stddev = vision::Tensor());
+/// A tracker's step: one frame, windows.size() search windows, ONE kernel
+/// launch.  results[i] = match_template(crop(src, windows[i]), target i,
+/// method) and, with `peaks`, (*peaks)[i] = its minMaxIdx, byte for byte what
+/// the three single calls give (vacv_match_template_rois).  src and targets
+/// INT8 NHWC, c <= 4.  The windows are truncated as crop() truncates them; all
+/// windows have one size and all targets one size; targets.size() is 1 (shared)
+/// or windows.size().  Anything else, a window outside the frame, a template
+/// larger than the window or a window too large for one workgroup's LDS
+/// throws.  A host frame, host templates and the origins are staged once
+/// through the pinned pool; device tensors stay where they are.  results and
+/// peaks are resized to windows.size(), each result with the placement of src.
+struct VMatchPeak { double minVal, maxVal; int minIdx[2], maxIdx[2]; };   // (row, col), as minMaxIdx
+void match_template(const vision::Tensor& src, const std::vector<vision::Tensor>& targets,
+                    const std::vector<vision::VRect>& windows, std::vector<vision::Tensor>& results,
+                    int method, std::vector<VMatchPeak>* peaks = nullptr);
 void cvt_color(const std::vector<vision::Tensor>& src, std::vector<vision::Tensor>& dst, int code);
 void cvt_color_normalize(const std::vector<vision::Tensor>& src, std::vector<vision::Tensor>& dst, int code,
                          const vision::Tensor& mean = vision::Tensor(),

@@ -693,6 +693,60 @@ def min_max_idx(src: torch.Tensor, mask: Optional[torch.Tensor] = None, stream=N
     return v[0], v[1], (i[0], i[1]), (i[2], i[3])
 
 
+_ORIGINS = ("origins", torch.int32, lambda a: a.dim() == 2 and a.shape[1] == 2, "(n, 2)", "origins holds no window")
+
+
+def search_origins(centers: torch.Tensor, w: int, h: int, frame_w: int, frame_h: int) -> torch.Tensor:
+    """(n, 2) centres (cx, cy), float32 or an integer dtype -> (n, 2) int32
+    origins (left, top) of the w x h search windows around them: (int(cx) -
+    w // 2, int(cy) - h // 2), a float centre truncated toward zero as crop
+    truncates a box, then clamped so that the window lies inside the frame_w x
+    frame_h frame.  Computed where `centers` lives."""
+    if not isinstance(centers, torch.Tensor) or centers.dim() != 2 or centers.shape[1] != 2:
+        raise ValueError("centers must be an (n, 2) tensor")
+    if centers.dtype != torch.float32 and (centers.dtype.is_floating_point or centers.dtype == torch.bool):
+        raise ValueError("centers must be float32 or an integer tensor")
+    if w < 1 or h < 1 or w > frame_w or h > frame_h:
+        raise ValueError(f"a {w} x {h} window does not fit a {frame_w} x {frame_h} frame")
+    c = centers.to(torch.int64)  # toward zero
+    left = (c[:, 0] - w // 2).clamp(0, frame_w - w)
+    top = (c[:, 1] - h // 2).clamp(0, frame_h - h)
+    return torch.stack([left, top], 1).to(torch.int32).contiguous()
+
+
+def match_template_rois(src: torch.Tensor, templ: torch.Tensor, origins, w: int, h: int, method: int,
+                        src_index=None, peaks: bool = True, out=None, stream=None):
+    """Many matches in one launch: result[i] = match_template(the w x h window
+    at origins[i] of src[src_index[i]], templ[i] or the one shared templ), and
+    with `peaks` its minMaxIdx.  u8 only.  src: NHWC frames (n, h, w, c) or one
+    (h, w, c) / (h, w) frame; templ: (th, tw, c) shared, or (n, th, tw, c) one
+    per ROI.  origins: (n, 2) int32 device tensor of (left, top) (search_origins
+    makes them from centres); src_index: (n,) int32 device tensor, or None (one
+    frame for all, or frame i for ROI i).  Both are read by the kernel when it
+    runs on `stream`, not by this call; a window outside its frame or a bad
+    index gives a map of zeros, vals (0, 0) and idx of -1s.
+    Returns (result, vals, idx): (n, h - th + 1, w - tw + 1) float32, (n, 2)
+    float64 (min, max) and (n, 4) int32 (min row, min col, max row, max col),
+    all on the device; or just result with peaks=False."""
+    s4, origins, src_index, n = _roi_batch(_as4d(src, NHWC), origins, *_ORIGINS, src_index)
+    t4 = _as4d(templ, NHWC)
+    th, tw = t4.shape[1], t4.shape[2]
+    if tw > w or th > h:
+        raise ValueError(f"match_template_rois: a {tw} x {th} template does not fit the {w} x {h} window")
+    rh, rw = h - th + 1, w - tw + 1
+    if out is None:
+        out = torch.empty((n, rh, rw), dtype=torch.float32, device=src.device)
+    elif tuple(out.shape) != (n, rh, rw):
+        raise ValueError(f"out must have shape {(n, rh, rw)}, got {tuple(out.shape)}")
+    vals = torch.empty((n, 2), dtype=torch.float64, device=src.device) if peaks else None
+    idx = torch.empty((n, 4), dtype=torch.int32, device=src.device) if peaks else None
+    check("vacv_match_template_rois", L.load().vacv_match_template_rois(
+        ctypes.byref(describe(s4, NHWC)), ctypes.byref(describe(t4, NHWC)),
+        ctypes.byref(describe(out.unsqueeze(-1), NHWC)), origins.data_ptr(), _idx_ptr(src_index), int(method),
+        vals.data_ptr() if peaks else None, idx.data_ptr() if peaks else None, _stream(stream)))
+    return (out, vals, idx) if peaks else out
+
+
 def set_tuning(name: str, value: int) -> int:
     """Select a kernel variant (VACV_TUNE_<name>, include/vacv_hip.h); value
     < 0 restores the built-in choice.  Returns the previous value."""

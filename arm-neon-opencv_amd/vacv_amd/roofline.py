@@ -193,6 +193,30 @@ def crop_resize_rois_bytes(c: int, in_esize: int, w_out: int, h_out: int, rects,
     return int(total)
 
 
+def match_template_rois_bytes(c: int, w: int, h: int, tw: int, th: int, origins, n_templ: int = 1,
+                              peaks: bool = True, w_in: int = None, h_in: int = None) -> int:
+    """B_alg of vacv_match_template_rois: per ROI the (w - tw + 1) x (h - th + 1)
+    fp32 map written and, with peaks, its 2 doubles and 4 int32; each valid
+    w x h search window's w * h * c source bytes, read once; and each of the
+    n_templ (1 = shared, or one per ROI) templates' tw * th * c bytes, read
+    once per ROI that uses it.  origins: (n, 2) of (left, top).  A window with
+    a negative origin or -- where the frame size w_in x h_in is given -- an
+    edge past the frame reads neither source nor template and counts its
+    outputs only."""
+    o = np.asarray(origins, dtype=np.int64).reshape(-1, 2)
+    if n_templ not in (1, o.shape[0]):
+        raise ValueError("n_templ is 1 or the number of ROIs")
+    per_roi = (w - tw + 1) * (h - th + 1) * 4 + (2 * 8 + 4 * 4 if peaks else 0)
+    total = o.shape[0] * per_roi
+    for left, top in o.tolist():
+        if left < 0 or top < 0:
+            continue
+        if (w_in is not None and left + w > w_in) or (h_in is not None and top + h > h_in):
+            continue
+        total += (w * h + tw * th) * c
+    return int(total)
+
+
 def yuv_crop_resize_rois_bytes(w_out: int, h_out: int, rects, out_esize: int = 1, w_in: int = None,
                                h_in: int = None) -> int:
     """B_alg of vacv_cvt_color_crop_resize_rois[_normalize]: the 3-channel

@@ -489,6 +489,54 @@ int vacv_match_template(const vacv_image* img, const vacv_image* templ, const va
  * and -1s.  NaNs are never selected. */
 int vacv_min_max_idx(const vacv_image* src, const vacv_image* mask, double* vals, int* idx, void* stream);
 
+/* A tracker's step in one launch: many templates matched in per-object search
+ * windows, with each result's peaks -- vacv_crop + vacv_match_template +
+ * vacv_min_max_idx per object, without the crops and in ONE kernel launch.
+ * INT8 only: FP32 is VACV_ERR_UNSUPPORTED (its window sums are order-dependent
+ * doubles and need a design of their own).
+ * src:    `src->n` frames, NHWC, INT8, c = 1..4, pitched (row and batch pitch)
+ *         or dense, any base alignment (NCHW: UNSUPPORTED).
+ * templ:  (tw, th, c) INT8 NHWC, pitched or dense.  templ->n == 1: one
+ *         template for every ROI; templ->n == result->n: template i for ROI i;
+ *         any other count: INVALID_ARG.
+ * result: `result->n` ROIs of (rw, rh, 1) FP32, pitched or dense.  Every
+ *         search window is W x H with W = rw + tw - 1, H = rh + th - 1.  There
+ *         is no template / image swap.
+ * origin:    DEVICE array [result->n][2] int32 {left, top} of each search
+ *            window in its frame.  NULL: INVALID_ARG.
+ * src_index: DEVICE array [result->n] int32, or NULL, with the NULL rules of
+ *            vacv_warp_affine_rois.
+ * vals:      DEVICE array [result->n][2] double {min, max}
+ * idx:       DEVICE array [result->n][4] int32 {min row, min col, max row,
+ *            max col}; vals and idx both given, or both NULL (only the maps
+ *            are written); one NULL: INVALID_ARG.
+ * method: VACV_TM_* (else UNSUPPORTED).
+ * All four arrays are used by the kernel, on `stream`, at execution time: the
+ * call queues one kernel, takes no workspace, copies nothing between host and
+ * device, never synchronizes, and host code never dereferences them.
+ * ROI i is byte-identical to vacv_match_template on the W x H vacv_crop at
+ * origin[i] of frame src_index[i] with template i; vals[i] / idx[i] are
+ * identical to vacv_min_max_idx (no mask) of that result.  Bytes of the result
+ * allocation outside the ROI rectangles are never written.
+ * Device-supplied values cannot fault: a window with left < 0, top < 0,
+ * left + W > src->w or top + H > src->h (the sums taken without int overflow),
+ * or a src_index[i] outside [0, src->n), gives a result of zeros, vals {0, 0}
+ * and idx {-1, -1, -1, -1} (vacv_min_max_idx's "no element") and reads no
+ * source byte; every other source read lies inside the validated window.
+ * VACV_ERR_UNSUPPORTED, with nothing written:
+ *  - tw * th > 66000 (the uint32 window sums' bound of vacv_match_template);
+ *  - a ROI that does not fit one workgroup's 64 KiB of LDS.  With
+ *    K4 = ceil(tw c / 4), G = ceil(rw / 4),
+ *    WS4 = max(ceil(W c / 4), (G - 1) c + K4 + floor(3 c / 4) + 2) | 1, the need is
+ *      256 + 4 (th K4 + H WS4 + H rw (c + 1)) bytes
+ *    (the template, the window, the window rows' horizontal sums);
+ *  - result->n > 16,777,215 (a workgroup per ROI).
+ * Order of the checks: descriptors and origin, then method / dtype / layout,
+ * then shapes, then these limits, then the vals / idx and src_index rules. */
+int vacv_match_template_rois(const vacv_image* src, const vacv_image* templ, const vacv_image* result,
+                             const int32_t* origin, const int32_t* src_index, int method,
+                             double* vals, int32_t* idx, void* stream);
+
 /* ---- runtime ---------------------------------------------------------- */
 
 /* Kernel-variant knobs, for A/B measurement and the parity tests that check

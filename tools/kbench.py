@@ -354,8 +354,33 @@ def main():
             yuv_crop_resize_rois_bytes(140, 210, rects7, 1, 1280, 720), 64 * 140 * 210)
         crop_chains["yuv_crop_resize_rois_720p_64x140x210_u8"] = dict(yuv=yuv7, rects=drects7, idx=None,
                                                                       out=torch.empty_like(o7), norm=False)
+    match_loops = {}
+    if a.op in ("match_rois", "all"):
+        # a tracker's step (vacv_match_template_rois): 256 objects on 8 frames,
+        # each its own 32 x 32 template in a 64 x 64 search window around a
+        # seeded centre, CCOEFF_NORMED, the peaks included
+        import numpy as np
+        from vacv_amd.roofline import match_template_rois_bytes
+        rng = np.random.default_rng(20261021)
+        src = frames(8, 1080, 1920)
+        tpls = frames(256, 32, 32)
+        centers = torch.from_numpy((rng.random((256, 2)) * [1920, 1080]).astype(np.float32)).to(dev)
+        dorg = ops.search_origins(centers, 64, 64, 1920, 1080)
+        idx = np.arange(256, dtype=np.int32) % 8
+        didx = torch.from_numpy(idx).to(dev)
+        o = torch.empty((256, 33, 33), dtype=torch.float32, device=dev)
+        method = vacv_amd._lib.TM_CCOEFF_NORMED
+        cases["match_rois_1080p_256x64x64_t32_ccoeff_normed"] = (
+            lambda src=src, tpls=tpls, dorg=dorg, didx=didx, o=o: ops.match_template_rois(
+                src, tpls, dorg, 64, 64, method, src_index=didx, out=o),
+            match_template_rois_bytes(3, 64, 64, 32, 32, dorg.cpu().numpy(), 256, True, 1920, 1080), 256 * 33 * 33)
+        match_loops["match_rois_1080p_256x64x64_t32_ccoeff_normed"] = dict(
+            src=src, tpls=tpls, origins=dorg.cpu().numpy(), idx=idx, w=64, h=64, method=method)
     if a.only:
         cases = {k: v for k, v in cases.items() if a.only in k}
+    if a.compare and a.op == "match_rois":
+        compare_with_match_loops({k: v for k, v in cases.items() if k in match_loops}, match_loops, a.iters)
+        return
     if a.compare and a.op == "yuv_crop_resize_rois":
         compare_with_crop_chains({k: v for k, v in cases.items() if k in crop_chains}, crop_chains, a.baseline_lib,
                                  a.iters)
@@ -717,6 +742,80 @@ def compare_with_crop_loops(cases, loops, iters):
             torch.cuda.synchronize()
             line["warp_rois_same_boxes_kernel_ms_median"] = round(events_ms(warp), 4)
         print(json.dumps(line), flush=True)
+
+
+def compare_with_match_loops(cases, loops, iters):
+    """--op match_rois: the one call against the same work as the loop it
+    replaces -- vacv_crop + vacv_match_template + vacv_min_max_idx per ROI on
+    this build (about 8 launches each) -- per case: both timed end to end with
+    a host clock around a synchronised stream, alternating, after warm-up; maps
+    and peaks compared equal.  The loop's descriptors, crop buffers and ctypes
+    references are built beforehand, so what is timed is the library.  Also the
+    one call's time between device events (the kernel)."""
+    import ctypes
+    import time
+
+    import torch
+    from vacv_amd import _lib as L, ops
+    lib = L.load()
+    stream = ops._stream()
+
+    for name, (fn, nbytes, px) in cases.items():
+        lp = loops[name]
+        src, tpls, origins, idx, w, h, method = (lp[k] for k in ("src", "tpls", "origins", "idx", "w", "h", "method"))
+        n, c = len(origins), src.shape[3]
+        rh, rw = h - tpls.shape[1] + 1, w - tpls.shape[2] + 1
+        dev = src.device
+        crops = torch.empty((n, h, w, c), dtype=torch.uint8, device=dev)
+        maps = torch.empty((n, rh, rw, 1), dtype=torch.float32, device=dev)
+        vals = torch.empty((n, 2), dtype=torch.float64, device=dev)
+        peaks = torch.empty((n, 4), dtype=torch.int32, device=dev)
+        keep = ([ops.describe(src[i:i + 1]) for i in range(src.shape[0])], [ops.describe(crops[i:i + 1]) for i in range(n)],
+                [ops.describe(tpls[i:i + 1]) for i in range(n)], [ops.describe(maps[i:i + 1]) for i in range(n)],
+                [ops.describe(maps[i, :, :, 0]) for i in range(n)])
+        fd, cd, td, md, m2 = ([ctypes.byref(d) for d in ds] for ds in keep)
+        vp = [vals[i].data_ptr() for i in range(n)]
+        ip = [peaks[i].data_ptr() for i in range(n)]
+        frame_of = [int(k) for k in idx]
+        lt = [(int(o[0]), int(o[1])) for o in origins]
+
+        def loop():
+            for i in range(n):
+                assert lib.vacv_crop(fd[frame_of[i]], cd[i], lt[i][0], lt[i][1], stream) == 0
+                assert lib.vacv_match_template(cd[i], td[i], md[i], method, stream) == 0
+                assert lib.vacv_min_max_idx(m2[i], None, vp[i], ip[i], stream) == 0
+
+        def timed(f):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            f()
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) * 1e3
+
+        for _ in range(5):
+            loop()
+            one = fn()
+        torch.cuda.synchronize()
+        same = bool(torch.equal(one[0], maps[..., 0]) and torch.equal(one[1], vals) and torch.equal(one[2], peaks))
+        t_loop, t_one = [], []
+        for _ in range(iters):
+            t_loop.append(timed(loop))
+            t_one.append(timed(fn))
+        ml, mo = sorted(t_loop)[iters // 2], sorted(t_one)[iters // 2]
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)]
+        s = torch.cuda.current_stream()
+        for e0, e1 in ev:
+            e0.record(s)
+            fn()
+            e1.record(s)
+        torch.cuda.synchronize()
+        kernel = sorted(e0.elapsed_time(e1) for e0, e1 in ev)[iters // 2]
+        print(json.dumps({"case": name, "rois": n, "frames": int(src.shape[0]), "baseline": "this build",
+                          "loop_ms_median": round(ml, 4), "loop_ms_min": round(min(t_loop), 4),
+                          "one_call_ms_median": round(mo, 4), "one_call_ms_min": round(min(t_one), 4),
+                          "loop_over_one_call": round(ml / mo, 2), "kernel_ms_median": round(kernel, 4),
+                          "alg_bytes": int(nbytes), "outputs_equal": same,
+                          "clock": "host, stream synchronised; kernel: events"}), flush=True)
 
 
 def run_cases(cases, iters, tag):
