@@ -1334,6 +1334,63 @@ int vacv_match_template_rois(const vacv_image* src_d, const vacv_image* tpl_d, c
     return hip_status(launch_match_rois(M, (hipStream_t)stream));
 }
 
+// ROI i = vacv_cvt_color of frame src_index[i], then vacv_match_template_rois
+// of the window at origin[i] of the decoded frame (k_yuv_match_rois.hip).  src
+// and code as yuv_rois_impl takes them, everything else as
+// vacv_match_template_rois, in its order: descriptors, origin; the code, the
+// method, the source's dtype / layout and the template's layout; the shapes;
+// the host-known limits; how the optional arrays pair up.
+int vacv_cvt_color_match_template_rois(const vacv_image* src_d, const vacv_image* tpl_d, const vacv_image* res_d,
+                                       int code, const int32_t* origin, const int32_t* src_index, int method,
+                                       double* vals, int32_t* idx, void* stream) {
+    Img src, tpl, res;
+    int st = load(src_d, src);
+    if (st) return st;
+    if ((st = load(tpl_d, tpl))) return st;
+    if ((st = load(res_d, res))) return st;
+    if (!origin) return VACV_ERR_INVALID_ARG;
+    int v_first, rgb;
+    if ((st = color_code(code, v_first, rgb))) return st;
+    if (method < VACV_TM_SQDIFF || method > VACV_TM_CCOEFF_NORMED) return VACV_ERR_UNSUPPORTED;
+    if (src.dtype != VACV_INT8 || src.c != 1 || src.layout != VACV_NHWC) return VACV_ERR_INVALID_ARG;
+    if (tpl.layout != VACV_NHWC) return VACV_ERR_UNSUPPORTED;
+    const int h = yuv420sp_height(src);
+    if (h < 0) return h;
+    if (tpl.dtype != VACV_INT8 || tpl.c != 3) return VACV_ERR_INVALID_ARG;  // the decoded frame's
+    if (tpl.n != 1 && tpl.n != res.n) return VACV_ERR_INVALID_ARG;
+    if (res.dtype != VACV_FP32 || res.c != 1) return VACV_ERR_INVALID_ARG;
+    if ((int64_t)tpl.w * tpl.h > 66000) return VACV_ERR_UNSUPPORTED;
+    if (match_rois_lds_bytes(tpl.w, tpl.h, 3, res.w, res.h) > 64 * 1024) return VACV_ERR_UNSUPPORTED;
+    if (res.n > (int)(UINT32_MAX / kBlock)) return VACV_ERR_UNSUPPORTED;
+    if (!vals != !idx) return VACV_ERR_INVALID_ARG;
+    if (!roi_frames_ok(src, res, src_index)) return VACV_ERR_INVALID_ARG;
+    MatchRoisLaunch M{};
+    M.src = geom(src);  // the YUV bytes' pitches ...
+    M.src.h = h;        // ... with the decoded size: what the kernel judges the windows against
+    M.src.cc = 3;
+    M.n_src = src.n;
+    M.n_roi = res.n;
+    M.tpl = tpl.data;
+    M.tpl_pitch = tpl.n == 1 ? 0 : tpl.batch;
+    M.tpl_row = tpl.row;
+    M.tw = tpl.w;
+    M.th = tpl.h;
+    M.res = res.data;
+    M.res_pitch = res.batch;
+    M.res_row = res.row;
+    M.rw = res.w;
+    M.rh = res.h;
+    M.origin = origin;
+    M.src_index = src_index;
+    M.method = method;
+    M.inv_area = 1. / ((double)tpl.h * tpl.w);
+    M.vals = vals;
+    M.idx = idx;
+    M.v_first = v_first;
+    M.rgb = rgb;
+    return hip_status(launch_yuv_match_rois(M, (hipStream_t)stream));
+}
+
 int vacv_min_max_idx(const vacv_image* src_d, const vacv_image* mask_d, double* vals, int* idx, void* stream) {
     Img src, mask;
     int st = load(src_d, src);

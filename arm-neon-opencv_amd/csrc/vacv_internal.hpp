@@ -445,9 +445,18 @@ struct MatchRoisLaunch {
     double inv_area;              // 1 / (tw * th)
     double* vals;                 // device [n_roi][2]: min, max; or null (with idx): no peaks
     int32_t* idx;                 // device [n_roi][4]: min row, min col, max row, max col
+    int v_first;                  // launch_yuv_match_rois only: NV21
+    int rgb;                      // launch_yuv_match_rois only: swap the decoded channel order
 };
 size_t match_rois_lds_bytes(int tw, int th, int cn, int rw, int rh);  // a workgroup's LDS (the host refuses > 64 KiB)
 hipError_t launch_match_rois(const MatchRoisLaunch& M, hipStream_t s);
+
+// The same from YUV420sp frames (k_yuv_match_rois.hip): ROI i = cvt_color of
+// frame src_index[i], then the match above in the decoded frame.  M.src
+// describes the YUV bytes with the decoded size: base = Y plane of frame 0,
+// img_pitch / row_pitch of the YUV buffer, w x h decoded, cc = 3; M.v_first
+// and M.rgb say how to decode
+hipError_t launch_yuv_match_rois(const MatchRoisLaunch& M, hipStream_t s);
 
 struct MinMaxLaunch {             // minMaxIdx of one single-channel image
     const unsigned char* src;

@@ -664,14 +664,24 @@ void minMaxIdx(const Tensor& src, double* minVal, double* maxVal, int* minIdx, i
     if (maxIdx) { maxIdx[0] = hi[2]; maxIdx[1] = hi[3]; }
 }
 
+namespace {
+
 // One frame, windows.size() matches and their peaks, one launch (RoiStage):
 // the origins and the templates go to HBM in one block (host templates through
 // the pinned pool, device templates copied into their place), the kernel
-// writes the maps back to back with the peaks behind them.
-void match_template(const Tensor& src, const std::vector<Tensor>& targets, const std::vector<VRect>& windows,
-                    std::vector<Tensor>& results, int method, std::vector<VMatchPeak>* peaks) {
-    static const char* fn = "va_cv::match_template";
+// writes the maps back to back with the peaks behind them.  yuv_code != 0: src
+// is a YUV420sp frame, the windows are taken from its decoded (w, h, 3) image
+// and the templates have its three channels (vacv_cvt_color_match_template_rois).
+void match_rois_into(const char* fn, const Tensor& src, const std::vector<Tensor>& targets,
+                     const std::vector<VRect>& windows, std::vector<Tensor>& results, int method,
+                     std::vector<VMatchPeak>* peaks, int yuv_code = 0) {
     if (src.empty()) fail(fn, "empty input tensor");
+    int fw = src.w, fh = src.h, fc = src.c;  // what the windows must lie in, and the templates' channels
+    if (yuv_code) {
+        check_yuv_code(fn, yuv_code);
+        fh = yuv_rows(fn, src);
+        fc = 3;
+    }
     if (src.dtype != INT8) fail(fn, "the matches of one frame take INT8");
     if (src.layout != NHWC) fail(fn, "the matches of one frame take an NHWC frame");
     if (windows.empty()) fail(fn, "empty window list");
@@ -681,7 +691,7 @@ void match_template(const Tensor& src, const std::vector<Tensor>& targets, const
     const Tensor& t0 = targets[0];
     if (t0.empty()) fail(fn, "empty template");
     for (const Tensor& t : targets) {
-        if (t.dtype != src.dtype || t.c != src.c || t.layout != NHWC)
+        if (t.dtype != src.dtype || t.c != fc || t.layout != NHWC)
             fail(fn, "every template must match the frame's dtype, channels and layout");
         if (t.w != t0.w || t.h != t0.h) fail(fn, "all templates must have one size");
     }
@@ -703,7 +713,7 @@ void match_template(const Tensor& src, const std::vector<Tensor>& targets, const
             wh = ch;
         }
         if (cw != ww || ch != wh) fail(fn, "all windows must have one size");
-        if (cw < 1 || ch < 1 || left < 0 || top < 0 || cw > src.w || left > src.w - cw || ch > src.h || top > src.h - ch)
+        if (cw < 1 || ch < 1 || left < 0 || top < 0 || cw > fw || left > fw - cw || ch > fh || top > fh - ch)
             fail(fn, "every window must lie inside the image");
         op[2 * i] = left;
         op[2 * i + 1] = top;
@@ -724,8 +734,12 @@ void match_template(const Tensor& src, const std::vector<Tensor>& targets, const
     const vacv_image rd = st.out(n, VSize(ww - t0.w + 1, wh - t0.h + 1), 1, FP32, peak_bytes);
     double* dv = peaks ? reinterpret_cast<double*>(st.tail_ptr) : nullptr;
     int32_t* di = peaks ? reinterpret_cast<int32_t*>(st.tail_ptr + n * 2 * sizeof(double)) : nullptr;
-    detail::check(fn, vacv_match_template_rois(&sd, &td, &rd, reinterpret_cast<const int32_t*>(dp), nullptr, method, dv,
-                                               di, st.s));
+    if (yuv_code)
+        detail::check(fn, vacv_cvt_color_match_template_rois(&sd, &td, &rd, yuv_code, reinterpret_cast<const int32_t*>(dp),
+                                                             nullptr, method, dv, di, st.s));
+    else
+        detail::check(fn, vacv_match_template_rois(&sd, &td, &rd, reinterpret_cast<const int32_t*>(dp), nullptr, method,
+                                                   dv, di, st.s));
     std::vector<unsigned char> hp(peak_bytes);
     if (peaks) detail::check_hip(fn, hipMemcpyAsync(hp.data(), st.tail_ptr, peak_bytes, hipMemcpyDeviceToHost, st.s));
     st.scatter(results, rd, src);
@@ -742,6 +756,18 @@ void match_template(const Tensor& src, const std::vector<Tensor>& targets, const
         p.maxIdx[0] = hi[4 * i + 2];
         p.maxIdx[1] = hi[4 * i + 3];
     }
+}
+
+}  // namespace
+
+void match_template(const Tensor& src, const std::vector<Tensor>& targets, const std::vector<VRect>& windows,
+                    std::vector<Tensor>& results, int method, std::vector<VMatchPeak>* peaks) {
+    match_rois_into("va_cv::match_template", src, targets, windows, results, method, peaks);
+}
+
+void cvt_color_match_template(const Tensor& yuv, const std::vector<Tensor>& targets, const std::vector<VRect>& windows,
+                              std::vector<Tensor>& results, int code, int method, std::vector<VMatchPeak>* peaks) {
+    match_rois_into("va_cv::cvt_color_match_template", yuv, targets, windows, results, method, peaks, code);
 }
 
 void imencode(const Tensor&, std::vector<unsigned char>&, const char*) {

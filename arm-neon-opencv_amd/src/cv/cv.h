@@ -274,6 +274,16 @@ struct VMatchPeak { double minVal, maxVal; int minIdx[2], maxIdx[2]; };   // (ro
 void match_template(const vision::Tensor& src, const std::vector<vision::Tensor>& targets,
                     const std::vector<vision::VRect>& windows, std::vector<vision::Tensor>& results,
                     int method, std::vector<VMatchPeak>* peaks = nullptr);
+/// The same step straight from one YUV420sp frame (w, h*3/2, 1) INT8 NHWC, ONE
+/// kernel launch and no decoded frame: results and peaks are bit for bit those
+/// of match_template(cvt_color(yuv, code), targets, windows, ...)
+/// (vacv_cvt_color_match_template_rois).  code: the NV21 / NV12 -> BGR / RGB
+/// codes; the windows lie in the decoded (w, h) frame and the targets are
+/// (tw, th, 3) INT8 NHWC in the decoded channel order.  Truncation, the
+/// throwing conditions and the placement of the results are the overload's above.
+void cvt_color_match_template(const vision::Tensor& yuv, const std::vector<vision::Tensor>& targets,
+                              const std::vector<vision::VRect>& windows, std::vector<vision::Tensor>& results,
+                              int code, int method, std::vector<VMatchPeak>* peaks = nullptr);
 void cvt_color(const std::vector<vision::Tensor>& src, std::vector<vision::Tensor>& dst, int code);
 void cvt_color_normalize(const std::vector<vision::Tensor>& src, std::vector<vision::Tensor>& dst, int code,
                          const vision::Tensor& mean = vision::Tensor(),

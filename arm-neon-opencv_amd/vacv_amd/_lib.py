@@ -105,6 +105,7 @@ SIGNATURES = {
     "vacv_match_template": ([_IMG, _IMG, _IMG, _I, _P], _I),
     "vacv_min_max_idx": ([_IMG, _IMG, _P, _P, _P], _I),
     "vacv_match_template_rois": ([_IMG, _IMG, _IMG, _P, _P, _I, _P, _P, _P], _I),
+    "vacv_cvt_color_match_template_rois": ([_IMG, _IMG, _IMG, _I, _P, _P, _I, _P, _P, _P], _I),
     "vacv_set_tuning": ([_I, _I], _I),
     "vacv_get_tuning": ([_I], _I),
 }
@@ -122,7 +123,8 @@ TUNE = {"RESIZE_DIRECT": 0, "CUBIC_DIRECT": 1, "RESIZE_INTERLEAVE": 2, "DIRECT_X
 # after round 5 added LANCZOS_KERNEL under version 2; 4: the ROI warp entry
 # points and vacv_invert_affine_device; 5: the ROI warp from YUV420sp frames).
 # An added export alone does not bump it (vacv_crop_resize_rois[_normalize],
-# vacv_cvt_color_crop_resize_rois[_normalize], vacv_match_template_rois).
+# vacv_cvt_color_crop_resize_rois[_normalize], vacv_match_template_rois,
+# vacv_cvt_color_match_template_rois).
 ABI_VERSION = 5
 
 _lib = None

@@ -747,6 +747,40 @@ def match_template_rois(src: torch.Tensor, templ: torch.Tensor, origins, w: int,
     return (out, vals, idx) if peaks else out
 
 
+def cvt_color_match_template_rois(yuv: torch.Tensor, templ: torch.Tensor, origins, w: int, h: int, method: int,
+                                  code: int = L.COLOR_YUV2BGR_NV21, src_index=None, peaks: bool = True, out=None,
+                                  stream=None):
+    """match_template_rois straight from NV21 / NV12 frames in one launch:
+    bit for bit match_template_rois(cvt_color(yuv, code), templ, ...), without
+    the decoded frames.  yuv: (n, h_in*3/2, w_in) u8 frames or one
+    (h_in*3/2, w_in) frame; templ: (th, tw, 3) or (n, th, tw, 3) u8 in the
+    decoded channel order of `code`; origins: (left, top) of the w x h windows
+    in the DECODED frame (search_origins with the decoded frame_w, frame_h).
+    Everything else, and what is returned, as match_template_rois."""
+    y4 = _yuv4(yuv)
+    _, origins, src_index, n = _roi_batch(_as4d(y4.unsqueeze(-1), NHWC), origins, *_ORIGINS, src_index)
+    if not isinstance(templ, torch.Tensor) or templ.device != yuv.device:
+        raise ValueError("templ must be a tensor on the frames' device")
+    if templ.dim() not in (3, 4) or templ.shape[-1] != 3:
+        raise ValueError(f"templ must have shape (th, tw, 3) or (n, th, tw, 3), got {tuple(templ.shape)}")
+    t4 = _as4d(templ, NHWC)
+    th, tw = t4.shape[1], t4.shape[2]
+    if tw > w or th > h:
+        raise ValueError(f"cvt_color_match_template_rois: a {tw} x {th} template does not fit the {w} x {h} window")
+    rh, rw = h - th + 1, w - tw + 1
+    if out is None:
+        out = torch.empty((n, rh, rw), dtype=torch.float32, device=yuv.device)
+    elif tuple(out.shape) != (n, rh, rw):
+        raise ValueError(f"out must have shape {(n, rh, rw)}, got {tuple(out.shape)}")
+    vals = torch.empty((n, 2), dtype=torch.float64, device=yuv.device) if peaks else None
+    idx = torch.empty((n, 4), dtype=torch.int32, device=yuv.device) if peaks else None
+    check("vacv_cvt_color_match_template_rois", L.load().vacv_cvt_color_match_template_rois(
+        ctypes.byref(_yuv_desc(y4)), ctypes.byref(describe(t4, NHWC)),
+        ctypes.byref(describe(out.unsqueeze(-1), NHWC)), int(code), origins.data_ptr(), _idx_ptr(src_index),
+        int(method), vals.data_ptr() if peaks else None, idx.data_ptr() if peaks else None, _stream(stream)))
+    return (out, vals, idx) if peaks else out
+
+
 def set_tuning(name: str, value: int) -> int:
     """Select a kernel variant (VACV_TUNE_<name>, include/vacv_hip.h); value
     < 0 restores the built-in choice.  Returns the previous value."""

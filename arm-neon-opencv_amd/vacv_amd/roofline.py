@@ -217,6 +217,29 @@ def match_template_rois_bytes(c: int, w: int, h: int, tw: int, th: int, origins,
     return int(total)
 
 
+def cvt_color_match_template_rois_bytes(w: int, h: int, tw: int, th: int, origins, n_templ: int = 1,
+                                        peaks: bool = True, w_in: int = None, h_in: int = None) -> int:
+    """B_alg of vacv_cvt_color_match_template_rois: the maps, the peaks and the
+    3-channel templates as match_template_rois_bytes counts them, and per
+    valid w x h search window (judged in the decoded w_in x h_in frame) its
+    w * h Y bytes and the chroma pairs that cover it -- columns left >> 1 to
+    (left + w - 1) >> 1 of chroma rows top >> 1 to (top + h - 1) >> 1, 2 bytes
+    each.  An invalid window reads nothing and counts its outputs only."""
+    o = np.asarray(origins, dtype=np.int64).reshape(-1, 2)
+    if n_templ not in (1, o.shape[0]):
+        raise ValueError("n_templ is 1 or the number of ROIs")
+    per_roi = (w - tw + 1) * (h - th + 1) * 4 + (2 * 8 + 4 * 4 if peaks else 0)
+    total = o.shape[0] * per_roi
+    for left, top in o.tolist():
+        if left < 0 or top < 0:
+            continue
+        if (w_in is not None and left + w > w_in) or (h_in is not None and top + h > h_in):
+            continue
+        total += w * h + tw * th * 3
+        total += 2 * (((left + w - 1) >> 1) - (left >> 1) + 1) * (((top + h - 1) >> 1) - (top >> 1) + 1)
+    return int(total)
+
+
 def yuv_crop_resize_rois_bytes(w_out: int, h_out: int, rects, out_esize: int = 1, w_in: int = None,
                                h_in: int = None) -> int:
     """B_alg of vacv_cvt_color_crop_resize_rois[_normalize]: the 3-channel

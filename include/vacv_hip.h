@@ -537,6 +537,46 @@ int vacv_match_template_rois(const vacv_image* src, const vacv_image* templ, con
                              const int32_t* origin, const int32_t* src_index, int method,
                              double* vals, int32_t* idx, void* stream);
 
+/* The same step straight from NV21 / NV12 camera frames: ROI i of the result,
+ * vals[i] and idx[i] are bit for bit what vacv_cvt_color(src, code) into
+ * (w, h, 3) INT8 frames followed by vacv_match_template_rois on those frames
+ * produces, in ONE kernel launch and without the decoded frames ever
+ * existing.  (Grey tracking needs no call of its own: describe the Y plane as
+ * c = 1 frames with the YUV row and batch pitch for vacv_match_template_rois.)
+ * src, code: exactly as vacv_cvt_color_warp_affine_rois -- `src->n` frames
+ *         (w, h * 3 / 2, 1) INT8 with w and h even and >= 2 (else
+ *         INVALID_ARG), pitched or dense, any base alignment; code one of
+ *         VACV_COLOR_YUV2{BGR,RGB}_NV{21,12} (every other code, the
+ *         OpenCV-arithmetic ones included: UNSUPPORTED).
+ * templ:  (tw, th, 3) INT8 NHWC in the decoded channel order of `code`,
+ *         pitched or dense; templ->n == 1 or templ->n == result->n (else
+ *         INVALID_ARG); c != 3 or another dtype: INVALID_ARG; NCHW: UNSUPPORTED.
+ * result, origin, src_index, method, vals, idx: exactly as
+ *         vacv_match_template_rois.  A window {left, top} is given in the
+ *         DECODED w x h frame.
+ * The call queues one kernel on `stream`, takes no workspace, copies nothing
+ * between host and device, never synchronizes, and host code never
+ * dereferences the four device arrays.  Bytes of the result allocation outside
+ * the ROI rectangles are never written.
+ * Device-supplied values cannot fault: a window with left < 0, top < 0,
+ * left + W > w or top + H > h (the decoded size; the sums taken without int
+ * overflow), or a src_index[i] outside [0, src->n), gives a result of zeros,
+ * vals {0, 0} and idx {-1, -1, -1, -1} and reads no source byte.  A valid
+ * window reads only bytes of its own Y rows, columns left .. left + W - 1, and
+ * of chroma rows h + (top >> 1) .. h + ((top + H - 1) >> 1), columns
+ * left & ~1 .. (left + W - 1) | 1: never a byte past a dense frame's last
+ * chroma pair.
+ * VACV_ERR_UNSUPPORTED, with nothing written: tw * th > 66000; a ROI whose
+ * need of LDS, vacv_match_template_rois's formula with c = 3, passes 64 KiB
+ * (the decode adds none); result->n > 16,777,215.
+ * Order of the checks: descriptors and origin; then code, method, the
+ * source's dtype / channels / layout and the template's layout; then shapes
+ * (the YUV size, the template's dtype / channels / count, the result); then
+ * these limits; then the vals / idx and src_index rules. */
+int vacv_cvt_color_match_template_rois(const vacv_image* src, const vacv_image* templ, const vacv_image* result,
+                                       int code, const int32_t* origin, const int32_t* src_index, int method,
+                                       double* vals, int32_t* idx, void* stream);
+
 /* ---- runtime ---------------------------------------------------------- */
 
 /* Kernel-variant knobs, for A/B measurement and the parity tests that check

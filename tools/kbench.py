@@ -31,7 +31,8 @@ def main():
                          "--op yuv_rois: against vacv_cvt_color of all frames + vacv_warp_affine_rois[_normalize]; "
                          "--op crop_resize_rois: against a loop of vacv_crop + vacv_resize[_normalize] single calls; "
                          "--op yuv_crop_resize_rois: against vacv_cvt_color of all frames + "
-                         "vacv_crop_resize_rois[_normalize]")
+                         "vacv_crop_resize_rois[_normalize]; "
+                         "--op yuv_match_rois: against vacv_cvt_color of all frames + vacv_match_template_rois")
     ap.add_argument("--baseline-lib", default="",
                     help="--compare: libvacv_hip.so of another build (e.g. the parent commit's) to run the loop on; "
                          "default: this build's own single-call entry points")
@@ -376,8 +377,31 @@ def main():
             match_template_rois_bytes(3, 64, 64, 32, 32, dorg.cpu().numpy(), 256, True, 1920, 1080), 256 * 33 * 33)
         match_loops["match_rois_1080p_256x64x64_t32_ccoeff_normed"] = dict(
             src=src, tpls=tpls, origins=dorg.cpu().numpy(), idx=idx, w=64, h=64, method=method)
+    match_chains = {}
+    if a.op in ("yuv_match_rois", "all"):
+        # the same step straight from NV21 frames (vacv_cvt_color_match_template_rois)
+        import numpy as np
+        from vacv_amd.roofline import cvt_color_match_template_rois_bytes
+        rng = np.random.default_rng(20261021)
+        yuv = torch.randint(0, 256, (8, 1620, 1920), dtype=torch.uint8, device=dev, generator=g)
+        tpls = frames(256, 32, 32)
+        centers = torch.from_numpy((rng.random((256, 2)) * [1920, 1080]).astype(np.float32)).to(dev)
+        dorg = ops.search_origins(centers, 64, 64, 1920, 1080)
+        didx = torch.from_numpy(np.arange(256, dtype=np.int32) % 8).to(dev)
+        o = torch.empty((256, 33, 33), dtype=torch.float32, device=dev)
+        method = vacv_amd._lib.TM_CCOEFF_NORMED
+        cases["yuv_match_rois_1080p_256x64x64_t32_ccoeff_normed"] = (
+            lambda yuv=yuv, tpls=tpls, dorg=dorg, didx=didx, o=o: ops.cvt_color_match_template_rois(
+                yuv, tpls, dorg, 64, 64, method, src_index=didx, out=o),
+            cvt_color_match_template_rois_bytes(64, 64, 32, 32, dorg.cpu().numpy(), 256, True, 1920, 1080),
+            256 * 33 * 33)
+        match_chains["yuv_match_rois_1080p_256x64x64_t32_ccoeff_normed"] = dict(
+            yuv=yuv, tpls=tpls, origins=dorg, idx=didx, w=64, h=64, method=method)
     if a.only:
         cases = {k: v for k, v in cases.items() if a.only in k}
+    if a.compare and a.op == "yuv_match_rois":
+        compare_with_match_chains({k: v for k, v in cases.items() if k in match_chains}, match_chains, a.iters)
+        return
     if a.compare and a.op == "match_rois":
         compare_with_match_loops({k: v for k, v in cases.items() if k in match_loops}, match_loops, a.iters)
         return
@@ -816,6 +840,103 @@ def compare_with_match_loops(cases, loops, iters):
                           "loop_over_one_call": round(ml / mo, 2), "kernel_ms_median": round(kernel, 4),
                           "alg_bytes": int(nbytes), "outputs_equal": same,
                           "clock": "host, stream synchronised; kernel: events"}), flush=True)
+
+
+def compare_with_match_chains(cases, chains, iters):
+    """--op yuv_match_rois: the one call against the chain it replaces --
+    vacv_cvt_color of all frames into a preallocated BGR buffer, then
+    vacv_match_template_rois on it, on this build (no line of either changed
+    with the fused call, so they are the parent commit's) -- per case: both
+    timed end to end with a host clock around a synchronised stream,
+    alternating, after warm-up; medians with p10-p90; maps, vals and idx compared
+    equal.  Both legs are ctypes calls whose descriptors were built beforehand,
+    so what is timed is the library.  Also between device events (the kernels):
+    the one call, vacv_cvt_color alone and vacv_match_template_rois alone."""
+    import ctypes
+    import time
+
+    import torch
+    from vacv_amd import _lib as L, ops
+    lib = L.load()
+    stream = ops._stream()
+    code = L.COLOR_YUV2BGR_NV21
+    by = ctypes.byref
+
+    def events_ms(f):
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)]
+        s = torch.cuda.current_stream()
+        for e0, e1 in ev:
+            e0.record(s)
+            f()
+            e1.record(s)
+        torch.cuda.synchronize()
+        return sorted(e0.elapsed_time(e1) for e0, e1 in ev)[iters // 2]
+
+    for name, (binding_call, nbytes, px) in cases.items():
+        ch = chains[name]
+        yuv, tpls, origins, idx, w, h, method = (ch[k] for k in ("yuv", "tpls", "origins", "idx", "w", "h", "method"))
+        n, dev = origins.shape[0], yuv.device
+        rh, rw = h - tpls.shape[1] + 1, w - tpls.shape[2] + 1
+        bgr = torch.empty((yuv.shape[0], yuv.shape[1] // 3 * 2, yuv.shape[2], 3), dtype=torch.uint8, device=dev)
+        maps = [torch.empty((n, rh, rw, 1), dtype=torch.float32, device=dev) for _ in range(2)]
+        vals = [torch.empty((n, 2), dtype=torch.float64, device=dev) for _ in range(2)]
+        peaks = [torch.empty((n, 4), dtype=torch.int32, device=dev) for _ in range(2)]
+        yd, bd, td = ops._yuv_desc(yuv), ops.describe(bgr), ops.describe(tpls)
+        md = [ops.describe(m) for m in maps]
+        op_, ip = origins.data_ptr(), idx.data_ptr()
+        vp, pp = [v.data_ptr() for v in vals], [p.data_ptr() for p in peaks]
+
+        def decode():
+            assert lib.vacv_cvt_color(by(yd), by(bd), code, stream) == 0
+
+        def match():
+            assert lib.vacv_match_template_rois(by(bd), by(td), by(md[0]), op_, ip, method, vp[0], pp[0], stream) == 0
+
+        def chain():
+            decode()
+            match()
+
+        def fn():
+            assert lib.vacv_cvt_color_match_template_rois(by(yd), by(td), by(md[1]), code, op_, ip, method, vp[1], pp[1],
+                                                          stream) == 0
+
+        def timed(f):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            f()
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) * 1e3
+
+        binding_call()  # the binding's own path works on the same operands
+        for t in maps + vals + peaks:
+            t.zero_()
+        for _ in range(20):
+            chain()
+            fn()
+        torch.cuda.synchronize()
+        same = bool(torch.equal(maps[0].view(torch.int32), maps[1].view(torch.int32)) and
+                    torch.equal(vals[0].view(torch.int64), vals[1].view(torch.int64)) and torch.equal(peaks[0], peaks[1]))
+        t_chain, t_one = [], []
+        for _ in range(iters):
+            t_chain.append(timed(chain))
+            t_one.append(timed(fn))
+        t_chain.sort()
+        t_one.sort()
+        mc, mo = t_chain[iters // 2], t_one[iters // 2]
+        k_one, k_decode, k_match = events_ms(fn), events_ms(decode), events_ms(match)
+        print(json.dumps({"case": name, "rois": int(n), "frames": int(yuv.shape[0]), "baseline": "this build",
+                          "iters": iters, "chain_ms_median": round(mc, 4), "chain_ms_min": round(t_chain[0], 4),
+                          "chain_ms_p10": round(t_chain[iters // 10], 4), "chain_ms_p90": round(t_chain[iters * 9 // 10], 4),
+                          "one_call_ms_median": round(mo, 4), "one_call_ms_min": round(t_one[0], 4),
+                          "one_call_ms_p10": round(t_one[iters // 10], 4),
+                          "one_call_ms_p90": round(t_one[iters * 9 // 10], 4),
+                          "chain_over_one_call": round(mc / mo, 2), "one_call_at_most_chain": bool(mo <= mc),
+                          "kernel_ms_median": round(k_one, 4), "cvt_color_kernel_ms_median": round(k_decode, 4),
+                          "match_rois_kernel_ms_median": round(k_match, 4),
+                          "kernel_at_most_sum": bool(k_one <= k_decode + k_match),
+                          "alg_bytes": int(nbytes), "one_call_alg_GBps": round(nbytes / mo / 1e6, 1),
+                          "outputs_equal": same,
+                          "clock": "host, stream synchronised; kernels: events"}), flush=True)
 
 
 def run_cases(cases, iters, tag):
