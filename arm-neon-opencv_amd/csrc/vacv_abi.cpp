@@ -611,6 +611,39 @@ int crop_resize_rois_impl(const vacv_image* src_d, const vacv_image* dst_d, cons
     return hip_status(launch_crop_resize_rois(L, s));
 }
 
+// vacv_crop_resize_rois_standardize: crop_resize_rois_impl's checks in its
+// order, with the INT8-only rule after roi_source's; then the work shape's own
+// limits (a ROI in one workgroup's LDS); then the output arrays.  mean_out /
+// stddev_out are device arrays: never read or written here.
+int crop_resize_rois_std_impl(const vacv_image* src_d, const vacv_image* dst_d, const int32_t* rects,
+                              const int32_t* src_index, int interpolation, int mode, float* mean_out,
+                              float* stddev_out, hipStream_t s) {
+    Img src, dst;
+    int st = load2(src_d, dst_d, src, dst);
+    if (st) return st;
+    if (!rects) return VACV_ERR_INVALID_ARG;
+    if (src.c != dst.c) return VACV_ERR_INVALID_ARG;
+    if (!roi_frames_ok(src, dst, src_index)) return VACV_ERR_INVALID_ARG;
+    if ((st = roi_source(src))) return st;
+    if (src.dtype != VACV_INT8) return VACV_ERR_UNSUPPORTED;  // fp32 sums are order-dependent
+    if (interpolation != VACV_INTER_LINEAR) return VACV_ERR_UNSUPPORTED;
+    if (mode < VACV_LINEAR_REFERENCE || mode > VACV_LINEAR_OPENCV) return VACV_ERR_INVALID_ARG;
+    if (!two_taps(src)) return VACV_ERR_INVALID_ARG;
+    bool planar;
+    const NormSpec own{};  // roi_output's and roi_fill's "normalized fp32"; its values are never used
+    if ((st = roi_output(dst, src.dtype, &own, planar))) return st;
+    CropResizeRoisStdLaunch L{};
+    L.src = geom(src);
+    roi_fill(L, src, dst, src_index, planar, &own);
+    L.rects = rects;
+    L.mode = mode;
+    L.mean_out = mean_out;
+    L.stddev_out = stddev_out;
+    if (!crop_resize_rois_std_fits(L)) return VACV_ERR_UNSUPPORTED;
+    if (mean_out && mean_out == stddev_out) return VACV_ERR_INVALID_ARG;  // one array for both
+    return hip_status(launch_crop_resize_rois_std(L, s));
+}
+
 int color_code(int code, int& v_first, int& rgb) {
     switch (code) {
         case VACV_COLOR_YUV2BGR_NV21: v_first = 1; rgb = 0; return VACV_OK;
@@ -1022,6 +1055,13 @@ int vacv_crop_resize_rois_normalize(const vacv_image* src, const vacv_image* dst
     const int st = roi_norm_spec(src, dst, mean, stddev, false, ns);
     if (st) return st;
     return crop_resize_rois_impl(src, dst, rects, src_index, interpolation, mode, &ns, (hipStream_t)stream);
+}
+
+int vacv_crop_resize_rois_standardize(const vacv_image* src, const vacv_image* dst, const int32_t* rects,
+                                      const int32_t* src_index, int interpolation, int mode, float* mean_out,
+                                      float* stddev_out, void* stream) {
+    return crop_resize_rois_std_impl(src, dst, rects, src_index, interpolation, mode, mean_out, stddev_out,
+                                     (hipStream_t)stream);
 }
 
 int vacv_warp_affine(const vacv_image* src, const vacv_image* dst, const float m[6], int flags, int border_mode,

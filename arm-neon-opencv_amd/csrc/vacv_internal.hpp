@@ -232,6 +232,16 @@ struct CropResizeRoisLaunch {
 };
 bool crop_resize_rois_fits(const CropResizeRoisLaunch& L);  // within the kernel's 32-bit indices
 hipError_t launch_crop_resize_rois(const CropResizeRoisLaunch& L, hipStream_t s);
+// ... each standardized by its own per-channel statistics, one workgroup per
+// ROI (k_crop_resize_rois_std.hip).  u8 frames, fp32 output; `out` is kOutNorm
+// and `norm` is unused: the statistics are the ROI's own
+struct CropResizeRoisStdLaunch : CropResizeRoisLaunch {
+    float* mean_out;             // device [n_roi][c], or null: not written
+    float* stddev_out;
+};
+size_t crop_resize_rois_std_lds_bytes(int w, int h, int c);  // a workgroup's LDS (the host refuses > 64 KiB)
+bool crop_resize_rois_std_fits(const CropResizeRoisStdLaunch& L);  // that, the 32-bit source offsets and grid
+hipError_t launch_crop_resize_rois_std(const CropResizeRoisStdLaunch& L, hipStream_t s);
 // u8 CONSTANT warp (1-4 interleaved channels, or NCHW planes) with the source boxes
 // copied into an LDS ring by LDS-DMA and the geometry shared by kf frames per
 // workgroup (k_warp_frames.hip)

@@ -509,9 +509,12 @@ namespace {
 
 // One launch for all crops (RoiStage) of the rects, truncated as crop() does.
 // yuv_code != 0: src is a YUV420sp frame and the rects are taken from its
-// decoded (w, h, 3) image (vacv_cvt_color_crop_resize_rois).
+// decoded (w, h, 3) image (vacv_cvt_color_crop_resize_rois).  own: every crop
+// standardized by its own statistics (vacv_crop_resize_rois_standardize), which
+// go to own_out = {mean, stddev}, host (c, n) FP32 tensors, when it is given.
 void crop_resize_into(const char* fn, const Tensor& src, std::vector<Tensor>& dst, const std::vector<VRect>& rects,
-                      VSize dsize, int interpolation, const Stats* stats, int yuv_code = 0) {
+                      VSize dsize, int interpolation, const Stats* stats, int yuv_code = 0, bool own = false,
+                      std::vector<Tensor>* own_out = nullptr) {
     if (src.empty()) fail(fn, "empty input tensor");
     int fw = src.w, fh = src.h;  // what the rects must lie in
     if (yuv_code) {
@@ -519,6 +522,7 @@ void crop_resize_into(const char* fn, const Tensor& src, std::vector<Tensor>& ds
         fh = yuv_rows(fn, src);
     }
     if (src.dtype != INT8 && src.dtype != FP32) fail(fn, "crop_resize takes INT8 or FP32");
+    if (own && src.dtype != INT8) fail(fn, "crops standardized by their own statistics take an INT8 frame");
     if (src.layout != NHWC) fail(fn, "the crops of one frame take an NHWC frame");
     if (interpolation != INTER_LINEAR) fail(fn, "only INTER_LINEAR is supported for the crops of one frame");
     if (dsize.w < 1 || dsize.h < 1) fail(fn, "dsize must be positive");
@@ -543,8 +547,18 @@ void crop_resize_into(const char* fn, const Tensor& src, std::vector<Tensor>& ds
     }
     const int32_t* dr = static_cast<const int32_t*>(st.params());
     const vacv_image sd = st.frame(src);
-    const vacv_image dd = st.out(n, dsize, yuv_code ? 3 : src.c, stats ? FP32 : src.dtype);
-    if (yuv_code && stats)
+    const size_t own_bytes = own_out ? n * src.c * sizeof(float) : 0;  // of each of the two arrays
+    const vacv_image dd = st.out(n, dsize, yuv_code ? 3 : src.c, stats || own ? FP32 : src.dtype, 2 * own_bytes);
+    std::vector<float> own_host(2 * own_bytes / sizeof(float));
+    if (own) {
+        float* dm = own_out ? reinterpret_cast<float*>(st.tail_ptr) : nullptr;
+        float* ds = own_out ? reinterpret_cast<float*>(st.tail_ptr + own_bytes) : nullptr;
+        // a crop past one workgroup's LDS is UNSUPPORTED: check() throws
+        detail::check(fn, vacv_crop_resize_rois_standardize(&sd, &dd, dr, nullptr, interpolation, VACV_LINEAR_REFERENCE,
+                                                            dm, ds, st.s));
+        if (own_out)
+            detail::check_hip(fn, hipMemcpyAsync(own_host.data(), st.tail_ptr, 2 * own_bytes, hipMemcpyDeviceToHost, st.s));
+    } else if (yuv_code && stats)
         detail::check(fn, vacv_cvt_color_crop_resize_rois_normalize(&sd, &dd, yuv_code, dr, nullptr, interpolation,
                                                                     VACV_LINEAR_REFERENCE, stats->m(), stats->s(), st.s));
     else if (yuv_code)
@@ -555,7 +569,14 @@ void crop_resize_into(const char* fn, const Tensor& src, std::vector<Tensor>& ds
                                                           stats->m(), stats->s(), st.s));
     else
         detail::check(fn, vacv_crop_resize_rois(&sd, &dd, dr, nullptr, interpolation, VACV_LINEAR_REFERENCE, st.s));
-    st.scatter(dst, dd, src);
+    st.scatter(dst, dd, src);  // waits for the stream
+    if (!own_out) return;
+    own_out->resize(2);
+    for (int k = 0; k < 2; ++k) {
+        (*own_out)[k].create(src.c, (int)n, FP32);
+        if (!(*own_out)[k].data) fail(fn, "out of memory creating the statistics");
+        std::memcpy((*own_out)[k].data, own_host.data() + k * (own_bytes / sizeof(float)), own_bytes);
+    }
 }
 
 }  // namespace
@@ -571,6 +592,11 @@ void crop_resize_normalize(const Tensor& src, std::vector<Tensor>& dst, const st
     const Stats stats = read_stats(fn, mean, stddev, src.c, false);
     if (!stats.m()) fail(fn, "the crops of one frame need mean and stddev (no per-image statistics)");
     crop_resize_into(fn, src, dst, rects, dsize, interpolation, &stats);
+}
+
+void crop_resize_standardize(const Tensor& src, std::vector<Tensor>& dst, const std::vector<VRect>& rects, VSize dsize,
+                              int interpolation, std::vector<Tensor>* stats) {
+    crop_resize_into("va_cv::crop_resize_standardize", src, dst, rects, dsize, interpolation, nullptr, 0, true, stats);
 }
 
 void cvt_color_crop_resize(const Tensor& yuv, std::vector<Tensor>& dst, const std::vector<VRect>& rects, int code,

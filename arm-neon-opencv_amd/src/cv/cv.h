@@ -247,6 +247,16 @@ void crop_resize_normalize(const vision::Tensor& src, std::vector<vision::Tensor
                            const std::vector<vision::VRect>& rects, VSize dsize, int interpolation = INTER_LINEAR,
                            const vision::Tensor& mean = vision::Tensor(),
                            const vision::Tensor& stddev = vision::Tensor());
+/// The same with every crop standardized by ITS OWN per-channel mean and
+/// standard deviation, ONE kernel launch: dst[i] is, bit for bit, crop() then
+/// resize() then normalize() with mean and stddev left empty (FP32 crops;
+/// vacv_crop_resize_rois_standardize).  src INT8 (an FP32 frame throws), and
+/// a crop must fit one workgroup's LDS -- 144 x 144 x 3 does; a larger dsize
+/// throws.  stats, when given, becomes {mean, stddev}: two host FP32 tensors
+/// (w = c, h = rects.size()), row i the statistics of crop i.
+void crop_resize_standardize(const vision::Tensor& src, std::vector<vision::Tensor>& dst,
+                             const std::vector<vision::VRect>& rects, VSize dsize, int interpolation = INTER_LINEAR,
+                             std::vector<vision::Tensor>* stats = nullptr);
 /// The same upright crops straight from one YUV420sp frame (w, h*3/2, 1) INT8
 /// NHWC, ONE kernel launch and no decoded frame: dst[i] = resize(crop(
 /// cvt_color(yuv, code), rects[i]), dsize), byte for byte, (w, h, 3) crops.

@@ -93,6 +93,7 @@ SIGNATURES = {
     "vacv_invert_affine_device": ([_P, _P, _I, _P], _I),
     "vacv_crop_resize_rois": ([_IMG, _IMG, _P, _P, _I, _I, _P], _I),
     "vacv_crop_resize_rois_normalize": ([_IMG, _IMG, _P, _P, _I, _I, _FP, _FP, _P], _I),
+    "vacv_crop_resize_rois_standardize": ([_IMG, _IMG, _P, _P, _I, _I, _P, _P, _P], _I),
     "vacv_cvt_color_normalize": ([_IMG, _IMG, _I, _FP, _FP, _P], _I),
     "vacv_cvt_color_resize": ([_IMG, _IMG, _I, _I, _I, _P], _I),
     "vacv_cvt_color_resize_normalize": ([_IMG, _IMG, _I, _I, _I, _FP, _FP, _P], _I),
@@ -124,7 +125,7 @@ TUNE = {"RESIZE_DIRECT": 0, "CUBIC_DIRECT": 1, "RESIZE_INTERLEAVE": 2, "DIRECT_X
 # points and vacv_invert_affine_device; 5: the ROI warp from YUV420sp frames).
 # An added export alone does not bump it (vacv_crop_resize_rois[_normalize],
 # vacv_cvt_color_crop_resize_rois[_normalize], vacv_match_template_rois,
-# vacv_cvt_color_match_template_rois).
+# vacv_cvt_color_match_template_rois, vacv_crop_resize_rois_standardize).
 ABI_VERSION = 5
 
 _lib = None

@@ -399,6 +399,35 @@ def crop_resize_rois_normalize(src: torch.Tensor, rects, w: int, h: int, mean, s
     return out
 
 
+def crop_resize_rois_standardize(src: torch.Tensor, rects, w: int, h: int, src_index=None,
+                                 mode: int = LINEAR_REFERENCE, layout: int = NHWC, out=None, stats: bool = False,
+                                 stream=None):
+    """crop_resize_rois with each crop standardized by its OWN per-channel mean
+    and standard deviation (the reference's resize_normalize of a crop with
+    mean and stddev left empty), in one launch: fp32 (n, h, w, c), or planar
+    (n, c, h, w) with layout=NCHW (c = 3 or 1).  src: uint8 frames.  Bit for
+    bit crop_resize_rois -> mean_stddev -> normalize(None, None) ->
+    change_layout; an invalid rect or index gives zeros with mean and stddev 0.
+    stats=True: returns (out, mean, std), the two (n, c) float32 device tensors
+    of every crop's statistics.  A crop must fit one workgroup's LDS (144 x 144
+    x 3 does): VacvError(UNSUPPORTED) otherwise."""
+    s4, rects, src_index, n = _roi_batch(_as4d(src, NHWC), rects, *_RECTS, src_index)
+    c = s4.shape[3]
+    if src.dtype != torch.uint8:
+        raise ValueError(f"crop_resize_rois_standardize takes uint8 frames, not {src.dtype}")
+    if out is None:
+        out = torch.empty((n, h, w, c) if layout == NHWC else (n, c, h, w), dtype=torch.float32, device=src.device)
+    mean = std = None
+    if stats:
+        mean = torch.empty((n, c), dtype=torch.float32, device=src.device)
+        std = torch.empty((n, c), dtype=torch.float32, device=src.device)
+    check("vacv_crop_resize_rois_standardize", L.load().vacv_crop_resize_rois_standardize(
+        ctypes.byref(describe(s4, NHWC)), ctypes.byref(describe(out, layout)), rects.data_ptr(),
+        _idx_ptr(src_index), INTER_LINEAR, mode, mean.data_ptr() if stats else None,
+        std.data_ptr() if stats else None, _stream(stream)))
+    return (out, mean, std) if stats else out
+
+
 # ---------------------------------------------------------------------------
 # colour
 

@@ -193,6 +193,15 @@ def crop_resize_rois_bytes(c: int, in_esize: int, w_out: int, h_out: int, rects,
     return int(total)
 
 
+def crop_resize_rois_standardize_bytes(c: int, w_out: int, h_out: int, rects, stats: bool = False,
+                                       w_in: int = None, h_in: int = None) -> int:
+    """B_alg of vacv_crop_resize_rois_standardize: crop_resize_rois_bytes of u8
+    frames and an fp32 output -- the u8 ROI and its statistics live in LDS and
+    cost no memory traffic -- plus, with stats, the two (n, c) fp32 arrays."""
+    n = np.asarray(rects, dtype=np.int64).reshape(-1, 4).shape[0]
+    return crop_resize_rois_bytes(c, 1, w_out, h_out, rects, 4, w_in, h_in) + (2 * n * c * 4 if stats else 0)
+
+
 def match_template_rois_bytes(c: int, w: int, h: int, tw: int, th: int, origins, n_templ: int = 1,
                               peaks: bool = True, w_in: int = None, h_in: int = None) -> int:
     """B_alg of vacv_match_template_rois: per ROI the (w - tw + 1) x (h - th + 1)

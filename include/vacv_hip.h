@@ -33,8 +33,8 @@ extern "C" {
 #endif
 
 /* Bumped when a signature, an enum value or the tuning enum changes.  An
- * added export alone does not bump it (vacv_crop_resize_rois[_normalize] came
- * under 5): a caller built against the older header still gets what it asked. */
+ * added export alone does not bump it (vacv_crop_resize_rois[_normalize] and
+ * vacv_crop_resize_rois_standardize came under 5): a caller built against the older header still gets what it asked. */
 #define VACV_ABI_VERSION 5
 #define VACV_MAX_CHANNELS 16
 
@@ -364,6 +364,62 @@ int vacv_crop_resize_rois(const vacv_image* src, const vacv_image* dst, const in
 int vacv_crop_resize_rois_normalize(const vacv_image* src, const vacv_image* dst, const int32_t* rects,
                                     const int32_t* src_index, int interpolation, int mode,
                                     const float* mean, const float* stddev, void* stream);
+/* The same, each ROI standardized by ITS OWN per-channel mean and standard
+ * deviation -- the reference's crop(src, box) then resize_normalize(crop, dst,
+ * dsize) with mean and stddev left empty (normalize.cpp:84-121,
+ * normalize_naive.cpp:7-72), the "prewhiten" input of face and re-ID
+ * embedders -- in ONE kernel launch.  (A function of its own: NULL / NULL of
+ * the _rois_normalize entry points stays UNSUPPORTED.)
+ * ROI i of dst and row i of mean_out / stddev_out are bit for bit what this
+ * chain gives:
+ *   1. vacv_crop_resize_rois(src, rects, src_index, INTER_LINEAR, mode) into a
+ *      dense INT8 NHWC batch u = [n][h][w][c];
+ *   2. vacv_mean_stddev(u): exact integer sums S1, S2 per ROI and channel, then
+ *      in fp64 m = S1 / (w h), var = max(S2 / (w h) - m m, 0), mean = (float)m,
+ *      stddev = (float)sqrt(var);
+ *   3. vacv_normalize(u -> FP32, NULL, NULL):
+ *      (float)((double)((float)v - mean) / ((double)stddev + 1e-6));
+ *   4. vacv_change_layout to NCHW when dst is NCHW.
+ * src: `src->n` frames, INT8, NHWC, c = 1..4, pitched or dense, any base
+ *      alignment: the INT8 frames vacv_crop_resize_rois takes.  FP32 frames:
+ *      UNSUPPORTED (their sums have vacv_channel_sums' summation order, which
+ *      another work shape cannot reproduce bit for bit).
+ * dst: `dst->n` ROIs of dst->w x dst->h, FP32, NHWC or NCHW (planar output for
+ *      c = 3 and c = 1; other channel counts: UNSUPPORTED), pitched or dense
+ *      (row, plane and batch pitch), at any 4-byte alignment.  INT8:
+ *      INVALID_ARG.
+ * rects, src_index: DEVICE arrays with exactly the rules of
+ *      vacv_crop_resize_rois (NULL rects: INVALID_ARG; the same NULL-index
+ *      rules), read by the kernel, on `stream`, at execution time.
+ * mean_out, stddev_out: DEVICE arrays [dst->n][c] float, written by the kernel;
+ *      either or both may be NULL, and a NULL array is not written.  The same
+ *      non-NULL pointer for both: INVALID_ARG.
+ * interpolation: INTER_LINEAR (else UNSUPPORTED).  mode: VACV_LINEAR_* (a value
+ * outside them: INVALID_ARG).
+ * The call queues one kernel, takes no workspace, copies nothing between host
+ * and device, allocates nothing and never synchronizes, and host code never
+ * dereferences the four device arrays.  Bytes of the dst allocation outside
+ * the ROI rectangles are never written.
+ * Device-supplied values cannot fault: a rect or index that
+ * vacv_crop_resize_rois calls invalid reads no source byte and is the chain's
+ * ROI of u8 zeros -- mean 0, stddev 0, every output +0.0; every other read is
+ * range-checked against the indexed frame by the hardware.
+ * VACV_ERR_UNSUPPORTED, with nothing written and before any HIP call:
+ *  - a ROI that does not fit one workgroup's 64 KiB of LDS.  The need is
+ *      256 + 16 ceil(w h c / 16) + max(8 (w + h), 1024 c) bytes
+ *    (a head, the u8 ROI, and the taps of all columns and rows or the table of
+ *    the 256 normalized values per channel, which share their bytes):
+ *    144 x 144 x 3 is exactly 64 KiB; 112 x 112 x 3 and 128 x 128 x 3 fit;
+ *  - a frame of 2 GiB or more;
+ *  - dst->n > 4,194,303 (a workgroup of 1,024 threads per ROI).
+ * Order of the checks: vacv_crop_resize_rois' own, in its order -- descriptors,
+ * rects, the channel counts, the src_index rule, the source's dtype / layout /
+ * channels (INT8 or FP32, NHWC, c <= 4; then FP32: UNSUPPORTED), interpolation,
+ * mode, the 2 x 2 source, dst's dtype, the planar channel counts -- then these
+ * limits, then mean_out == stddev_out. */
+int vacv_crop_resize_rois_standardize(const vacv_image* src, const vacv_image* dst, const int32_t* rects,
+                                      const int32_t* src_index, int interpolation, int mode,
+                                      float* mean_out, float* stddev_out, void* stream);
 
 /* cvt_color then normalize (the cfg3 pipeline), dst (w,h,3) FP32 NHWC. */
 int vacv_cvt_color_normalize(const vacv_image* src, const vacv_image* dst, int code,

@@ -29,7 +29,8 @@ def main():
                     help="--op warp_rois: time each one-call case against the same crops as a loop of single "
                          "calls (vacv_warp_affine; vacv_warp_affine_normalize + one vacv_change_layout), alternating; "
                          "--op yuv_rois: against vacv_cvt_color of all frames + vacv_warp_affine_rois[_normalize]; "
-                         "--op crop_resize_rois: against a loop of vacv_crop + vacv_resize[_normalize] single calls; "
+                         "--op crop_resize_rois: against a loop of vacv_crop + vacv_resize[_normalize] single calls "
+                         "(the standardize case: against crop_resize_rois + normalize(NULL, NULL) + change_layout); "
                          "--op yuv_crop_resize_rois: against vacv_cvt_color of all frames + "
                          "vacv_crop_resize_rois[_normalize]; "
                          "--op yuv_match_rois: against vacv_cvt_color of all frames + vacv_match_template_rois")
@@ -272,7 +273,7 @@ def main():
             lambda yuv7=yuv7, dms7=dms7, o7=o7: ops.cvt_color_warp_affine_rois(yuv7, dms7, 140, 210, out=o7),
             yuv_warp_rois_bytes(1280, 720, 140, 210, ms7), 64 * 140 * 210)
         chains["yuv_rois_720p_64x140x210_u8"] = dict(yuv=yuv7, ms=dms7, idx=None, out=torch.empty_like(o7), norm=False)
-    crop_loops = {}
+    crop_loops, std_chains = {}, {}
     if a.op in ("crop_resize_rois", "all"):
         # many upright crops, each with its own rect, in ONE launch
         # (vacv_crop_resize_rois): seeded boxes of 32..400 pixels per side
@@ -314,6 +315,17 @@ def main():
             crop_resize_rois_bytes(3, 1, 140, 210, rects7, 1), 64 * 140 * 210)
         crop_loops["crop_resize_rois_720p_64x140x210_u8"] = dict(src=src7, rects=rects7, idx=np.zeros(64, np.int32),
                                                                  out=torch.empty_like(o7), norm=False)
+        # the same boxes, each crop standardized by its own statistics
+        # (vacv_crop_resize_rois_standardize); the comparator is the chain it
+        # replaces, into preallocated buffers
+        from vacv_amd.roofline import crop_resize_rois_standardize_bytes
+        os_ = torch.empty((256, 3, 112, 112), dtype=torch.float32, device=dev)
+        cases["crop_resize_rois_standardize_1080p_256x112_chw"] = (
+            lambda src=src, drects=drects, didx=didx, os_=os_: ops.crop_resize_rois_standardize(
+                src, drects, 112, 112, src_index=didx, layout=vacv_amd.NCHW, out=os_),
+            crop_resize_rois_standardize_bytes(3, 112, 112, rects, False, 1920, 1080), 256 * 112 * 112)
+        std_chains["crop_resize_rois_standardize_1080p_256x112_chw"] = dict(src=src, rects=drects, idx=didx,
+                                                                            out=torch.empty_like(os_))
     crop_chains = {}
     if a.op in ("yuv_crop_resize_rois", "all"):
         # the crop_resize_rois cases with NV21 frames as the source
@@ -411,6 +423,7 @@ def main():
         return
     if a.compare and a.op == "crop_resize_rois":
         compare_with_crop_loops({k: v for k, v in cases.items() if k in crop_loops}, crop_loops, a.iters)
+        compare_with_std_chains({k: v for k, v in cases.items() if k in std_chains}, std_chains, a.iters)
         return
     if a.compare and a.op == "yuv_rois":
         compare_with_chains({k: v for k, v in cases.items() if k in chains}, chains, a.baseline_lib, a.iters)
@@ -766,6 +779,79 @@ def compare_with_crop_loops(cases, loops, iters):
             torch.cuda.synchronize()
             line["warp_rois_same_boxes_kernel_ms_median"] = round(events_ms(warp), 4)
         print(json.dumps(line), flush=True)
+
+
+def compare_with_std_chains(cases, chains, iters):
+    """--op crop_resize_rois, the standardize case: the one call against the
+    chain it replaces on this build -- ops.crop_resize_rois into a u8 batch,
+    ops.normalize(None, None) (the per-image statistics and the normalize) into
+    an fp32 NHWC batch, ops.change_layout into the NCHW output, every buffer
+    preallocated -- both timed end to end with a host clock around a
+    synchronised stream, alternating, after warm-up; medians with p10-p90,
+    outputs compared equal.  Also the one call's time between device events
+    (the kernel)."""
+    import time
+
+    import torch
+    import vacv_amd
+    from vacv_amd import ops
+
+    def timed(f):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        f()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    for name, (fn, nbytes, px) in cases.items():
+        ch = chains[name]
+        src, rects, idx, out = ch["src"], ch["rects"], ch["idx"], ch["out"]
+        n, c, ho, wo = out.shape
+        u = torch.empty((n, ho, wo, c), dtype=torch.uint8, device=out.device)
+        f32 = torch.empty((n, ho, wo, c), dtype=torch.float32, device=out.device)
+
+        def chain():
+            ops.crop_resize_rois(src, rects, wo, ho, src_index=idx, out=u)
+            ops.normalize(u, None, None, out=f32)
+            ops.change_layout(f32, vacv_amd.NCHW, out=out)
+
+        for _ in range(20):
+            chain()
+            one = fn()
+        torch.cuda.synchronize()
+        same = bool(torch.equal(one.view(torch.int32), out.view(torch.int32)))  # bit for bit
+        t_chain, t_one = [], []
+        for _ in range(iters):
+            t_chain.append(timed(chain))
+            t_one.append(timed(fn))
+        t_chain.sort()
+        t_one.sort()
+        mc, mo = t_chain[iters // 2], t_one[iters // 2]
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)]
+        s = torch.cuda.current_stream()
+        for e0, e1 in ev:
+            e0.record(s)
+            fn()
+            e1.record(s)
+        torch.cuda.synchronize()
+        kernel = sorted(e0.elapsed_time(e1) for e0, e1 in ev)[iters // 2]
+        evc = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)]
+        for e0, e1 in evc:
+            e0.record(s)
+            chain()
+            e1.record(s)
+        torch.cuda.synchronize()
+        chain_ev = sorted(e0.elapsed_time(e1) for e0, e1 in evc)[iters // 2]
+        print(json.dumps({"case": name, "rois": int(n), "frames": int(src.shape[0]), "baseline": "this build",
+                          "iters": iters, "chain_ms_median": round(mc, 4), "chain_ms_min": round(t_chain[0], 4),
+                          "chain_ms_p10": round(t_chain[iters // 10], 4), "chain_ms_p90": round(t_chain[iters * 9 // 10], 4),
+                          "one_call_ms_median": round(mo, 4), "one_call_ms_min": round(t_one[0], 4),
+                          "one_call_ms_p10": round(t_one[iters // 10], 4),
+                          "one_call_ms_p90": round(t_one[iters * 9 // 10], 4),
+                          "chain_over_one_call": round(mc / mo, 2), "kernel_ms_median": round(kernel, 4),
+                          "chain_events_ms_median": round(chain_ev, 4), "alg_bytes": int(nbytes),
+                          "kernel_alg_GBps": round(nbytes / kernel / 1e6, 1), "outputs_equal": same,
+                          "clock": "host, stream synchronised; kernel and chain_events: device events"}), flush=True)
 
 
 def compare_with_match_loops(cases, loops, iters):
