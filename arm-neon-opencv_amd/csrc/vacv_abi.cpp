@@ -585,6 +585,38 @@ int warp_rois_impl(const vacv_image* src_d, const vacv_image* dst_d, const float
     return hip_status(launch_warp_rois(L, s));
 }
 
+// vacv_warp_affine_rois_standardize: warp_rois_impl's checks in its order, with
+// the INT8-only rule after roi_source's; then the work shape's own limits (a
+// ROI in one workgroup's LDS); then the output arrays.  mean_out / stddev_out
+// are device arrays: never read or written here.
+int warp_rois_std_impl(const vacv_image* src_d, const vacv_image* dst_d, const float* m, const int32_t* src_index,
+                       int flags, int border_mode, const double bv[4], float* mean_out, float* stddev_out,
+                       hipStream_t s) {
+    Img src, dst;
+    int st = load2(src_d, dst_d, src, dst);
+    if (st) return st;
+    if (!m) return VACV_ERR_INVALID_ARG;
+    if (src.c != dst.c) return VACV_ERR_INVALID_ARG;
+    if (!roi_frames_ok(src, dst, src_index)) return VACV_ERR_INVALID_ARG;
+    if ((st = roi_source(src))) return st;
+    if (src.dtype != VACV_INT8) return VACV_ERR_UNSUPPORTED;  // fp32 sums are order-dependent
+    if ((st = rois_options(flags, border_mode))) return st;
+    if (!two_taps(src)) return VACV_ERR_INVALID_ARG;
+    bool planar;
+    const NormSpec own{};  // roi_output's and roi_fill's "normalized fp32"; its values are never used
+    if ((st = roi_output(dst, src.dtype, &own, planar))) return st;
+    WarpRoisStdLaunch L{};
+    L.src = geom(src);
+    if (L.src.plane_bytes > kMaxPlaneBytes) return VACV_ERR_UNSUPPORTED;
+    roi_fill(L, src, dst, src_index, planar, &own);
+    roi_fill_warp(L, src, m, flags, border_mode, bv);
+    L.mean_out = mean_out;
+    L.stddev_out = stddev_out;
+    if (!warp_rois_std_fits(L)) return VACV_ERR_UNSUPPORTED;
+    if (mean_out && mean_out == stddev_out) return VACV_ERR_INVALID_ARG;  // one array for both
+    return hip_status(launch_warp_rois_std(L, s));
+}
+
 // vacv_crop_resize_rois[_normalize]: dst image i = rect rects[i] of src image
 // src_index[i], resized to dst->w x dst->h.  rects and src_index are device
 // arrays: validated for presence only, never read here.  ns as warp_rois_impl.
@@ -1041,6 +1073,14 @@ int vacv_warp_affine_rois_normalize(const vacv_image* src, const vacv_image* dst
     const int st = roi_norm_spec(src, dst, mean, stddev, false, ns);
     if (st) return st;
     return warp_rois_impl(src, dst, m, src_index, flags, border_mode, border_value, &ns, (hipStream_t)stream);
+}
+
+int vacv_warp_affine_rois_standardize(const vacv_image* src, const vacv_image* dst, const float* m,
+                                      const int32_t* src_index, int flags, int border_mode,
+                                      const double border_value[4], float* mean_out, float* stddev_out,
+                                      void* stream) {
+    return warp_rois_std_impl(src, dst, m, src_index, flags, border_mode, border_value, mean_out, stddev_out,
+                              (hipStream_t)stream);
 }
 
 int vacv_crop_resize_rois(const vacv_image* src, const vacv_image* dst, const int32_t* rects, const int32_t* src_index,

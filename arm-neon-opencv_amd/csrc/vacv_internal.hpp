@@ -216,6 +216,16 @@ struct WarpRoisLaunch {
 };
 hipError_t launch_warp_rois(const WarpRoisLaunch& L, hipStream_t s);
 hipError_t launch_invert_affine(const float* m, float* inv, int n, hipStream_t s);
+// ... each standardized by its own per-channel statistics, one workgroup per
+// ROI (k_warp_rois_std.hip).  u8 frames, fp32 output; `out` is kOutNorm and
+// `norm` is unused: the statistics are the ROI's own
+struct WarpRoisStdLaunch : WarpRoisLaunch {
+    float* mean_out;             // device [n_roi][c], or null: not written
+    float* stddev_out;
+};
+size_t warp_rois_std_lds_bytes(int w, int h, int c);  // a workgroup's LDS (the host refuses > 64 KiB)
+bool warp_rois_std_fits(const WarpRoisStdLaunch& L);  // that and the grid
+hipError_t launch_warp_rois_std(const WarpRoisStdLaunch& L, hipStream_t s);
 // Many upright crops in one launch (k_crop_resize_rois.hip): ROI i = bilinear
 // resize of rect rects[i] of frame src_index[i] with the rect's own taps;
 // both arrays are device memory read by the kernel

@@ -423,17 +423,32 @@ struct RoiStage {
     }
 };
 
+// The crops' own statistics, n rows of c floats each of mean then stddev in
+// `host`, as {mean, stddev}: two host (c, n) FP32 tensors
+void own_stats_out(const char* fn, std::vector<Tensor>& out, const std::vector<float>& host, int c, size_t n) {
+    out.resize(2);
+    for (int k = 0; k < 2; ++k) {
+        out[k].create(c, (int)n, FP32);
+        if (!out[k].data) fail(fn, "out of memory creating the statistics");
+        std::memcpy(out[k].data, host.data() + k * n * c, n * c * sizeof(float));
+    }
+}
+
 // One launch for all crops (RoiStage); each matrix is taken from where it
 // lives.  yuv_code != 0: src is a YUV420sp frame and the crops are taken from
-// its decoded (w, h, 3) image (vacv_cvt_color_warp_affine_rois).
+// its decoded (w, h, 3) image (vacv_cvt_color_warp_affine_rois).  own: every
+// crop standardized by its own statistics (vacv_warp_affine_rois_standardize),
+// which go to own_out = {mean, stddev} (own_stats_out) when it is given.
 void warp_rois_into(const char* fn, const Tensor& src, std::vector<Tensor>& dst, const std::vector<Tensor>& M,
-                    VSize dsize, int flags, int borderMode, const VScalar& bv, const Stats* stats, int yuv_code = 0) {
+                    VSize dsize, int flags, int borderMode, const VScalar& bv, const Stats* stats, int yuv_code = 0,
+                    bool own = false, std::vector<Tensor>* own_out = nullptr) {
     if (src.empty()) fail(fn, "empty input tensor");
     if (yuv_code) {
         check_yuv_code(fn, yuv_code);
         (void)yuv_rows(fn, src);
     }
     if (src.dtype != INT8 && src.dtype != FP32) fail(fn, "warp_affine takes INT8 or FP32");
+    if (own && src.dtype != INT8) fail(fn, "crops standardized by their own statistics take an INT8 frame");
     if (src.layout != NHWC) fail(fn, "the crops of one frame take an NHWC frame");
     if ((flags & ~(INTER_MAX | WARP_INVERSE_MAP)) || (flags & INTER_MAX) != INTER_LINEAR)
         fail(fn, "only INTER_LINEAR (optionally | WARP_INVERSE_MAP) is supported for the crops of one frame");
@@ -458,9 +473,18 @@ void warp_rois_into(const char* fn, const Tensor& src, std::vector<Tensor>& dst,
         if (M[i].on_device())
             detail::check_hip(fn, hipMemcpyAsync(dm + 6 * i, M[i].data, 6 * sizeof(float), hipMemcpyDeviceToDevice, s));
     const vacv_image sd = st.frame(src);
-    const vacv_image dd = st.out(n, dsize, yuv_code ? 3 : src.c, stats ? FP32 : src.dtype);
+    const size_t own_bytes = own_out ? n * src.c * sizeof(float) : 0;  // of each of the two arrays
+    const vacv_image dd = st.out(n, dsize, yuv_code ? 3 : src.c, stats || own ? FP32 : src.dtype, 2 * own_bytes);
+    std::vector<float> own_host(2 * own_bytes / sizeof(float));
     const double border[4] = {bv.v0, bv.v1, bv.v2, bv.v3};
-    if (yuv_code && stats)
+    if (own) {
+        float* om = own_out ? reinterpret_cast<float*>(st.tail_ptr) : nullptr;
+        float* os = own_out ? reinterpret_cast<float*>(st.tail_ptr + own_bytes) : nullptr;
+        // a crop past one workgroup's LDS is UNSUPPORTED: check() throws
+        detail::check(fn, vacv_warp_affine_rois_standardize(&sd, &dd, dm, nullptr, flags, borderMode, border, om, os, s));
+        if (own_out)
+            detail::check_hip(fn, hipMemcpyAsync(own_host.data(), st.tail_ptr, 2 * own_bytes, hipMemcpyDeviceToHost, s));
+    } else if (yuv_code && stats)
         detail::check(fn, vacv_cvt_color_warp_affine_rois_normalize(&sd, &dd, yuv_code, dm, nullptr, flags, borderMode,
                                                                     border, stats->m(), stats->s(), s));
     else if (yuv_code)
@@ -470,7 +494,8 @@ void warp_rois_into(const char* fn, const Tensor& src, std::vector<Tensor>& dst,
                                                           stats->s(), s));
     else
         detail::check(fn, vacv_warp_affine_rois(&sd, &dd, dm, nullptr, flags, borderMode, border, s));
-    st.scatter(dst, dd, src);
+    st.scatter(dst, dd, src);  // waits for the stream
+    if (own_out) own_stats_out(fn, *own_out, own_host, src.c, n);
 }
 
 }  // namespace
@@ -487,6 +512,12 @@ void warp_affine_normalize(const Tensor& src, std::vector<Tensor>& dst, const st
     const Stats stats = read_stats(fn, mean, stddev, src.c, false);
     if (!stats.m()) fail(fn, "the crops of one frame need mean and stddev (no per-image statistics)");
     warp_rois_into(fn, src, dst, M, dsize, flags, borderMode, borderValue, &stats);
+}
+
+void warp_affine_standardize(const Tensor& src, std::vector<Tensor>& dst, const std::vector<Tensor>& M, VSize dsize,
+                              int flags, int borderMode, const VScalar& borderValue, std::vector<Tensor>* stats) {
+    warp_rois_into("va_cv::warp_affine_standardize", src, dst, M, dsize, flags, borderMode, borderValue, nullptr, 0, true,
+                   stats);
 }
 
 void cvt_color_warp_affine(const Tensor& yuv, std::vector<Tensor>& dst, const std::vector<Tensor>& M, int code,
@@ -511,7 +542,7 @@ namespace {
 // yuv_code != 0: src is a YUV420sp frame and the rects are taken from its
 // decoded (w, h, 3) image (vacv_cvt_color_crop_resize_rois).  own: every crop
 // standardized by its own statistics (vacv_crop_resize_rois_standardize), which
-// go to own_out = {mean, stddev}, host (c, n) FP32 tensors, when it is given.
+// go to own_out = {mean, stddev} (own_stats_out) when it is given.
 void crop_resize_into(const char* fn, const Tensor& src, std::vector<Tensor>& dst, const std::vector<VRect>& rects,
                       VSize dsize, int interpolation, const Stats* stats, int yuv_code = 0, bool own = false,
                       std::vector<Tensor>* own_out = nullptr) {
@@ -570,13 +601,7 @@ void crop_resize_into(const char* fn, const Tensor& src, std::vector<Tensor>& ds
     else
         detail::check(fn, vacv_crop_resize_rois(&sd, &dd, dr, nullptr, interpolation, VACV_LINEAR_REFERENCE, st.s));
     st.scatter(dst, dd, src);  // waits for the stream
-    if (!own_out) return;
-    own_out->resize(2);
-    for (int k = 0; k < 2; ++k) {
-        (*own_out)[k].create(src.c, (int)n, FP32);
-        if (!(*own_out)[k].data) fail(fn, "out of memory creating the statistics");
-        std::memcpy((*own_out)[k].data, own_host.data() + k * (own_bytes / sizeof(float)), own_bytes);
-    }
+    if (own_out) own_stats_out(fn, *own_out, own_host, src.c, n);
 }
 
 }  // namespace

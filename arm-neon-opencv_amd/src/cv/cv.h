@@ -218,6 +218,18 @@ void warp_affine_normalize(const vision::Tensor& src, std::vector<vision::Tensor
                            int borderMode = BORDER_CONSTANT, const VScalar& borderValue = VScalar(),
                            const vision::Tensor& mean = vision::Tensor(),
                            const vision::Tensor& stddev = vision::Tensor());
+/// The same with every crop standardized by ITS OWN per-channel mean and
+/// standard deviation, ONE kernel launch: dst[i] is, bit for bit,
+/// warp_affine(src, M[i], dsize) then normalize() with mean and stddev left
+/// empty (FP32 crops; border pixels count in the statistics;
+/// vacv_warp_affine_rois_standardize).  src INT8 (an FP32 frame throws), and
+/// a crop must fit one workgroup's LDS -- 144 x 144 x 3 does; a larger dsize
+/// throws.  stats, when given, becomes {mean, stddev}: two host FP32 tensors
+/// (w = c, h = M.size()), row i the statistics of crop i.
+void warp_affine_standardize(const vision::Tensor& src, std::vector<vision::Tensor>& dst,
+                             const std::vector<vision::Tensor>& M, VSize dsize, int flags = INTER_LINEAR,
+                             int borderMode = BORDER_CONSTANT, const VScalar& borderValue = VScalar(),
+                             std::vector<vision::Tensor>* stats = nullptr);
 /// The same crops straight from one YUV420sp frame (w, h*3/2, 1) INT8 NHWC,
 /// ONE kernel launch and no decoded frame: dst[i] = warp_affine(cvt_color(yuv,
 /// code), M[i], dsize), byte for byte, (w, h, 3) crops.  code: the NV21 / NV12

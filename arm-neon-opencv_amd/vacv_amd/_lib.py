@@ -90,6 +90,7 @@ SIGNATURES = {
     "vacv_warp_affine_normalize": ([_IMG, _IMG, _FP, _I, _I, _DP, _FP, _FP, _P], _I),
     "vacv_warp_affine_rois": ([_IMG, _IMG, _P, _P, _I, _I, _DP, _P], _I),
     "vacv_warp_affine_rois_normalize": ([_IMG, _IMG, _P, _P, _I, _I, _DP, _FP, _FP, _P], _I),
+    "vacv_warp_affine_rois_standardize": ([_IMG, _IMG, _P, _P, _I, _I, _DP, _P, _P, _P], _I),
     "vacv_invert_affine_device": ([_P, _P, _I, _P], _I),
     "vacv_crop_resize_rois": ([_IMG, _IMG, _P, _P, _I, _I, _P], _I),
     "vacv_crop_resize_rois_normalize": ([_IMG, _IMG, _P, _P, _I, _I, _FP, _FP, _P], _I),
@@ -125,7 +126,8 @@ TUNE = {"RESIZE_DIRECT": 0, "CUBIC_DIRECT": 1, "RESIZE_INTERLEAVE": 2, "DIRECT_X
 # points and vacv_invert_affine_device; 5: the ROI warp from YUV420sp frames).
 # An added export alone does not bump it (vacv_crop_resize_rois[_normalize],
 # vacv_cvt_color_crop_resize_rois[_normalize], vacv_match_template_rois,
-# vacv_cvt_color_match_template_rois, vacv_crop_resize_rois_standardize).
+# vacv_cvt_color_match_template_rois, vacv_crop_resize_rois_standardize,
+# vacv_warp_affine_rois_standardize).
 ABI_VERSION = 5
 
 _lib = None

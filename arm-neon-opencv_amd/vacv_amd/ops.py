@@ -329,6 +329,37 @@ def warp_affine_rois_normalize(src: torch.Tensor, ms, w: int, h: int, mean, std,
     return out
 
 
+def warp_affine_rois_standardize(src: torch.Tensor, ms, w: int, h: int, src_index=None, flags: int = INTER_LINEAR,
+                                 border_mode: int = BORDER_CONSTANT, border_value=(0, 0, 0, 0), layout: int = NHWC,
+                                 out=None, stats: bool = False, stream=None):
+    """warp_affine_rois with each crop standardized by its OWN per-channel mean
+    and standard deviation (the reference's warp_affine_normalize with mean and
+    stddev left empty), in one launch: fp32 (n, h, w, c), or planar
+    (n, c, h, w) with layout=NCHW (c = 3 or 1).  src: uint8 frames.  Bit for
+    bit warp_affine_rois -> mean_stddev -> normalize(None, None) ->
+    change_layout: border pixels count in the statistics, and an index outside
+    the frames gives zeros with mean = border_value and stddev 0.
+    stats=True: returns (out, mean, std), the two (n, c) float32 device tensors
+    of every crop's statistics.  A crop must fit one workgroup's LDS (144 x 144
+    x 3 does): VacvError(UNSUPPORTED) otherwise."""
+    s4, ms, src_index, n = _roi_batch(_as4d(src, NHWC), ms, *_MS, src_index)
+    c = s4.shape[3]
+    if src.dtype != torch.uint8:
+        raise ValueError(f"warp_affine_rois_standardize takes uint8 frames, not {src.dtype}")
+    if out is None:
+        out = torch.empty((n, h, w, c) if layout == NHWC else (n, c, h, w), dtype=torch.float32, device=src.device)
+    mean = std = None
+    if stats:
+        mean = torch.empty((n, c), dtype=torch.float32, device=src.device)
+        std = torch.empty((n, c), dtype=torch.float32, device=src.device)
+    bv, bp = _border(border_value)
+    check("vacv_warp_affine_rois_standardize", L.load().vacv_warp_affine_rois_standardize(
+        ctypes.byref(describe(s4, NHWC)), ctypes.byref(describe(out, layout)), ms.data_ptr(),
+        _idx_ptr(src_index), flags, border_mode, bp, mean.data_ptr() if stats else None,
+        std.data_ptr() if stats else None, _stream(stream)))
+    return (out, mean, std) if stats else out
+
+
 def invert_affine_device(ms: torch.Tensor, out=None, stream=None) -> torch.Tensor:
     """vacv_invert_affine of every map of a float32 device tensor (n, 6) or
     (n, 2, 3), on the device (bit-identical to the host function)."""

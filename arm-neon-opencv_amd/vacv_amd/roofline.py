@@ -172,6 +172,15 @@ def warp_rois_bytes(w_in: int, h_in: int, c: int, w_out: int, h_out: int, ms, in
     return int(total)
 
 
+def warp_affine_rois_standardize_bytes(w_in: int, h_in: int, c: int, w_out: int, h_out: int, ms,
+                                       stats: bool = False, inverse_map: bool = False) -> int:
+    """B_alg of vacv_warp_affine_rois_standardize: warp_rois_bytes of u8 frames
+    and an fp32 output -- the u8 ROI and its statistics live in LDS and cost no
+    memory traffic -- plus, with stats, the two (n, c) fp32 arrays."""
+    n = np.asarray(ms, dtype=np.float64).reshape(-1, 6).shape[0]
+    return warp_rois_bytes(w_in, h_in, c, w_out, h_out, ms, 1, 4, inverse_map) + (2 * n * c * 4 if stats else 0)
+
+
 def crop_resize_rois_bytes(c: int, in_esize: int, w_out: int, h_out: int, rects, out_esize: int = 1,
                            w_in: int = None, h_in: int = None) -> int:
     """B_alg of vacv_crop_resize_rois[_normalize]: the output bytes of every

@@ -34,7 +34,7 @@ extern "C" {
 
 /* Bumped when a signature, an enum value or the tuning enum changes.  An
  * added export alone does not bump it (vacv_crop_resize_rois[_normalize] and
- * vacv_crop_resize_rois_standardize came under 5): a caller built against the older header still gets what it asked. */
+ * the two _rois_standardize functions came under 5): a caller built against the older header still gets what it asked. */
 #define VACV_ABI_VERSION 5
 #define VACV_MAX_CHANNELS 16
 
@@ -314,6 +314,67 @@ int vacv_warp_affine_rois_normalize(const vacv_image* src, const vacv_image* dst
                                     const int32_t* src_index, int flags, int border_mode,
                                     const double border_value[4],
                                     const float* mean, const float* stddev, void* stream);
+/* The same, each ROI standardized by ITS OWN per-channel mean and standard
+ * deviation -- the reference's warp_affine_normalize with mean and stddev left
+ * empty (warp_affine_normalize.cpp:145-164), the "prewhiten" input of face
+ * embedders: align each face with its own similarity map, then whiten the
+ * aligned crop -- in ONE kernel launch.  (A function of its own: NULL / NULL
+ * of the _rois_normalize entry points stays UNSUPPORTED.)
+ * ROI i of dst and row i of mean_out / stddev_out are bit for bit what this
+ * chain gives:
+ *   1. vacv_warp_affine_rois(src, m, src_index, flags, border_mode,
+ *      border_value) into a dense INT8 NHWC batch u = [n][h][w][c]; border
+ *      pixels are part of the ROI and count in its statistics, as in the
+ *      reference;
+ *   2. vacv_mean_stddev(u): exact integer sums S1, S2 per ROI and channel, then
+ *      in fp64 m = S1 / (w h), var = max(S2 / (w h) - m m, 0), mean = (float)m,
+ *      stddev = (float)sqrt(var);
+ *   3. vacv_normalize(u -> FP32, NULL, NULL):
+ *      (float)((double)((float)v - mean) / ((double)stddev + 1e-6));
+ *   4. vacv_change_layout to NCHW when dst is NCHW.
+ * src: `src->n` frames, INT8, NHWC, c = 1..4, pitched or dense, any base
+ *      alignment: the INT8 frames vacv_warp_affine_rois takes.  FP32 frames:
+ *      UNSUPPORTED (their sums have vacv_channel_sums' summation order, which
+ *      another work shape cannot reproduce bit for bit).
+ * dst: `dst->n` ROIs of dst->w x dst->h, FP32, NHWC or NCHW (planar output for
+ *      c = 3 and c = 1; other channel counts: UNSUPPORTED), pitched or dense
+ *      (row, plane and batch pitch), at any 4-byte alignment.  INT8:
+ *      INVALID_ARG.
+ * m, src_index, flags, border_mode, border_value: exactly the rules of
+ *      vacv_warp_affine_rois (m and src_index are DEVICE arrays read by the
+ *      kernel, on `stream`, at execution time; NULL m: INVALID_ARG; the same
+ *      NULL-index rules; INTER_LINEAR, optionally | VACV_WARP_INVERSE_MAP;
+ *      CONSTANT, REPLICATE, REFLECT, WRAP or REFLECT_101, TRANSPARENT:
+ *      UNSUPPORTED).
+ * mean_out, stddev_out: DEVICE arrays [dst->n][c] float, written by the kernel;
+ *      either or both may be NULL, and a NULL array is not written.  The same
+ *      non-NULL pointer for both: INVALID_ARG.
+ * The call queues one kernel, takes no workspace, copies nothing between host
+ * and device, allocates nothing and never synchronizes, and host code never
+ * dereferences the four device arrays.  Bytes of the dst allocation outside
+ * the ROI rectangles are never written.
+ * Device-supplied values cannot fault: a src_index[i] outside [0, src->n)
+ * reads no source byte and is the chain's ROI of border_value -- mean = the u8
+ * border value per channel, stddev 0, every output +0.0; zero-determinant and
+ * non-finite maps behave as vacv_warp_affine_rois documents; every sampler
+ * read goes through a buffer resource that spans exactly the indexed frame.
+ * VACV_ERR_UNSUPPORTED, with nothing written and before any HIP call:
+ *  - a ROI that does not fit one workgroup's 64 KiB of LDS.  The need is
+ *      256 + 16 ceil(w h c / 16) + 1024 c bytes
+ *    (a head, the u8 ROI and the table of the 256 normalized values per
+ *    channel): 144 x 144 x 3 is exactly 64 KiB; 112 x 112 x 3 and
+ *    128 x 128 x 3 fit; one channel fits up to 64,256 pixels;
+ *  - a frame of 2 GiB or more;
+ *  - dst->n > 4,194,303 (a workgroup of 1,024 threads per ROI).
+ * Order of the checks: vacv_warp_affine_rois' own, in its order -- descriptors,
+ * m, the channel counts, the src_index rule, the source's dtype / layout /
+ * channels (INT8 or FP32, NHWC, c <= 4; then FP32: UNSUPPORTED), flags and
+ * border_mode, the 2 x 2 source, dst's dtype, the planar channel counts, the
+ * frame's size -- then the LDS and grid limits, then mean_out == stddev_out. */
+int vacv_warp_affine_rois_standardize(const vacv_image* src, const vacv_image* dst, const float* m,
+                                      const int32_t* src_index, int flags, int border_mode,
+                                      const double border_value[4],
+                                      float* mean_out, float* stddev_out, void* stream);
 /* inv[i] = vacv_invert_affine(m[i]) for n maps, bit for bit.  DEVICE in,
  * DEVICE out, queued on `stream`. */
 int vacv_invert_affine_device(const float* m, float* inv, int n, void* stream);

@@ -27,7 +27,8 @@ def main():
                          "e.g. 'DIRECT_ALIGN=0,1;RESIZE_WORK=2,4'")
     ap.add_argument("--compare", action="store_true",
                     help="--op warp_rois: time each one-call case against the same crops as a loop of single "
-                         "calls (vacv_warp_affine; vacv_warp_affine_normalize + one vacv_change_layout), alternating; "
+                         "calls (vacv_warp_affine; vacv_warp_affine_normalize + one vacv_change_layout), alternating "
+                         "(the standardize case: against warp_affine_rois + normalize(NULL, NULL) + change_layout); "
                          "--op yuv_rois: against vacv_cvt_color of all frames + vacv_warp_affine_rois[_normalize]; "
                          "--op crop_resize_rois: against a loop of vacv_crop + vacv_resize[_normalize] single calls "
                          "(the standardize case: against crop_resize_rois + normalize(NULL, NULL) + change_layout); "
@@ -185,7 +186,7 @@ def main():
         src = frames(n, 360, 640)
         cases["hwc_to_chw_640x360_u8"] = (lambda src=src: ops.change_layout(src, vacv_amd.NCHW),
                                           n * 640 * 360 * 6, n * 640 * 360)
-    loops = {}
+    loops, std_chains = {}, {}
     if a.op in ("warp_rois", "all"):
         # many small crops, each with its own matrix, in ONE launch
         # (vacv_warp_affine_rois): seeded geometry -- rotation uniform in +-30
@@ -230,6 +231,18 @@ def main():
             warp_rois_bytes(1280, 720, 3, 140, 210, ms7), 64 * 140 * 210)
         loops["warp_rois_720p_64x140x210_u8"] = dict(src=src7, ms=ms7, idx=np.zeros(64, np.int32),
                                                      out=torch.empty_like(o7), norm=False)
+        # the 1080p maps, each crop standardized by its own statistics
+        # (vacv_warp_affine_rois_standardize); the comparator is the chain it
+        # replaces, into preallocated buffers
+        from vacv_amd.roofline import warp_affine_rois_standardize_bytes
+        os_ = torch.empty((256, 3, 112, 112), dtype=torch.float32, device=dev)
+        cases["warp_rois_standardize_1080p_256x112_chw"] = (
+            lambda src=src, dms=dms, didx=didx, os_=os_: ops.warp_affine_rois_standardize(
+                src, dms, 112, 112, src_index=didx, layout=vacv_amd.NCHW, out=os_),
+            warp_affine_rois_standardize_bytes(1920, 1080, 3, 112, 112, ms), 256 * 112 * 112)
+        std_chains["warp_rois_standardize_1080p_256x112_chw"] = dict(
+            frames=8, out=torch.empty_like(os_),
+            u8=lambda u, src=src, dms=dms, didx=didx: ops.warp_affine_rois(src, dms, 112, 112, src_index=didx, out=u))
     chains = {}
     if a.op in ("yuv_rois", "all"):
         # the warp_rois cases with NV21 frames as the source
@@ -273,7 +286,7 @@ def main():
             lambda yuv7=yuv7, dms7=dms7, o7=o7: ops.cvt_color_warp_affine_rois(yuv7, dms7, 140, 210, out=o7),
             yuv_warp_rois_bytes(1280, 720, 140, 210, ms7), 64 * 140 * 210)
         chains["yuv_rois_720p_64x140x210_u8"] = dict(yuv=yuv7, ms=dms7, idx=None, out=torch.empty_like(o7), norm=False)
-    crop_loops, std_chains = {}, {}
+    crop_loops = {}
     if a.op in ("crop_resize_rois", "all"):
         # many upright crops, each with its own rect, in ONE launch
         # (vacv_crop_resize_rois): seeded boxes of 32..400 pixels per side
@@ -324,8 +337,10 @@ def main():
             lambda src=src, drects=drects, didx=didx, os_=os_: ops.crop_resize_rois_standardize(
                 src, drects, 112, 112, src_index=didx, layout=vacv_amd.NCHW, out=os_),
             crop_resize_rois_standardize_bytes(3, 112, 112, rects, False, 1920, 1080), 256 * 112 * 112)
-        std_chains["crop_resize_rois_standardize_1080p_256x112_chw"] = dict(src=src, rects=drects, idx=didx,
-                                                                            out=torch.empty_like(os_))
+        std_chains["crop_resize_rois_standardize_1080p_256x112_chw"] = dict(
+            frames=8, out=torch.empty_like(os_),
+            u8=lambda u, src=src, drects=drects, didx=didx: ops.crop_resize_rois(src, drects, 112, 112, src_index=didx,
+                                                                                out=u))
     crop_chains = {}
     if a.op in ("yuv_crop_resize_rois", "all"):
         # the crop_resize_rois cases with NV21 frames as the source
@@ -430,6 +445,7 @@ def main():
         return
     if a.compare:
         compare_with_loops({k: v for k, v in cases.items() if k in loops}, loops, a.baseline_lib, a.iters)
+        compare_with_std_chains({k: v for k, v in cases.items() if k in std_chains}, std_chains, a.iters)
         return
     import itertools
     knobs = [kv.split("=", 1) for kv in a.sweep.split(";") if kv]
@@ -782,8 +798,9 @@ def compare_with_crop_loops(cases, loops, iters):
 
 
 def compare_with_std_chains(cases, chains, iters):
-    """--op crop_resize_rois, the standardize case: the one call against the
-    chain it replaces on this build -- ops.crop_resize_rois into a u8 batch,
+    """--op crop_resize_rois and --op warp_rois, the standardize cases: the one
+    call against the chain it replaces on this build -- ops.crop_resize_rois or
+    ops.warp_affine_rois (the chain's "u8" stage) into a u8 batch,
     ops.normalize(None, None) (the per-image statistics and the normalize) into
     an fp32 NHWC batch, ops.change_layout into the NCHW output, every buffer
     preallocated -- both timed end to end with a host clock around a
@@ -805,13 +822,13 @@ def compare_with_std_chains(cases, chains, iters):
 
     for name, (fn, nbytes, px) in cases.items():
         ch = chains[name]
-        src, rects, idx, out = ch["src"], ch["rects"], ch["idx"], ch["out"]
+        first, out = ch["u8"], ch["out"]
         n, c, ho, wo = out.shape
         u = torch.empty((n, ho, wo, c), dtype=torch.uint8, device=out.device)
         f32 = torch.empty((n, ho, wo, c), dtype=torch.float32, device=out.device)
 
         def chain():
-            ops.crop_resize_rois(src, rects, wo, ho, src_index=idx, out=u)
+            first(u)
             ops.normalize(u, None, None, out=f32)
             ops.change_layout(f32, vacv_amd.NCHW, out=out)
 
@@ -842,7 +859,7 @@ def compare_with_std_chains(cases, chains, iters):
             e1.record(s)
         torch.cuda.synchronize()
         chain_ev = sorted(e0.elapsed_time(e1) for e0, e1 in evc)[iters // 2]
-        print(json.dumps({"case": name, "rois": int(n), "frames": int(src.shape[0]), "baseline": "this build",
+        print(json.dumps({"case": name, "rois": int(n), "frames": int(ch["frames"]), "baseline": "this build",
                           "iters": iters, "chain_ms_median": round(mc, 4), "chain_ms_min": round(t_chain[0], 4),
                           "chain_ms_p10": round(t_chain[iters // 10], 4), "chain_ms_p90": round(t_chain[iters * 9 // 10], 4),
                           "one_call_ms_median": round(mo, 4), "one_call_ms_min": round(t_one[0], 4),
