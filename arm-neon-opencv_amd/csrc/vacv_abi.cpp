@@ -1175,8 +1175,11 @@ int resize_sums(const vacv_image* src_d, const vacv_image* dst_d, int interpolat
     Img src, dst;
     int st = load2(src_d, dst_d, src, dst);
     if (st) return st;
+    // the sums are taken over one dense range per image: a pitched dst, which vacv_channel_sums
+    // refuses, is refused here, before the resize writes it
+    if (!dense(dst)) return VACV_ERR_UNSUPPORTED;
     if (interpolation == VACV_INTER_CUBIC && src.dtype == VACV_INT8 && dst.dtype == VACV_FP32 &&
-        dst.layout == VACV_NHWC && dst.c <= 3 && dense(dst) && src.n == dst.n) {
+        dst.layout == VACV_NHWC && dst.c <= 3 && src.n == dst.n) {
         const int64_t groups = cubic_sums_groups_bound(dst.w, dst.h);  // the workspace's bound
         void* ws = nullptr;
         void* acc = nullptr;

@@ -851,6 +851,11 @@ def set_tuning(name: str, value: int) -> int:
     return old
 
 
+def release_workspace() -> None:
+    """vacv_release_workspace: frees the per-stream workspaces and the cached plans and tables; the next call rebuilds them."""
+    check("vacv_release_workspace", L.load().vacv_release_workspace())
+
+
 class tuning:
     """Context manager: `with ops.tuning(WARP_KERNEL=0): ...` runs the block
     with those kernel variants and restores the previous choices after."""

@@ -227,7 +227,8 @@ int vacv_channel_sums(const vacv_image* src, double* sums, int per_image, void* 
 /* vacv_resize followed by vacv_channel_sums of its output: the statistics
  * half of BASELINE cfg5 (resize + mean_stddev, normalize_naive.cpp:7-72 on
  * the resized image); on several GPUs the sums are what one all-reduce
- * merges.  dst must be dense. */
+ * merges.  dst must be dense (VACV_ERR_UNSUPPORTED otherwise, and nothing
+ * is written). */
 int vacv_resize_channel_sums(const vacv_image* src, const vacv_image* dst, int interpolation, int mode,
                              double* sums, int per_image, void* stream);
 
@@ -237,7 +238,8 @@ int vacv_resize_channel_sums(const vacv_image* src, const vacv_image* dst, int i
  * image, else 1) -- resize_naive.cpp:130-569, then NormalizeNaive::
  * mean_stddev_naive_* (normalize_naive.cpp:7-48) over the image or the whole
  * batch.  On several GPUs use vacv_resize_channel_sums, all-reduce the sums,
- * then vacv_stats_from_sums.  dst must be dense. */
+ * then vacv_stats_from_sums.  dst must be dense (VACV_ERR_UNSUPPORTED
+ * otherwise, and nothing is written). */
 int vacv_resize_mean_stddev(const vacv_image* src, const vacv_image* dst, int interpolation, int mode,
                             double* sums, float* mean, float* stddev, int per_image, void* stream);
 
