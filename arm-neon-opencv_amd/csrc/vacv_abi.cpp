@@ -888,6 +888,88 @@ int yuv_crop_resize_rois_impl(const vacv_image* src_d, const vacv_image* dst_d, 
     return hip_status(launch_yuv_crop_resize_rois(L, s));
 }
 
+// vacv_cvt_color_warp_affine_rois_standardize: yuv_rois_impl's checks in its
+// order; then the work shape's own limits (a ROI in one workgroup's LDS); then
+// the output arrays.  mean_out / stddev_out are device arrays: never read or
+// written here.
+int yuv_warp_rois_std_impl(const vacv_image* src_d, const vacv_image* dst_d, int code, const float* m,
+                           const int32_t* src_index, int flags, int border_mode, const double bv[4], float* mean_out,
+                           float* stddev_out, hipStream_t s) {
+    Img src, dst;
+    int st = load2(src_d, dst_d, src, dst);
+    if (st) return st;
+    if (!m) return VACV_ERR_INVALID_ARG;
+    int v_first, rgb;
+    if ((st = color_code(code, v_first, rgb))) return st;
+    if (src.dtype != VACV_INT8 || src.c != 1 || src.layout != VACV_NHWC) return VACV_ERR_INVALID_ARG;
+    const int h = yuv420sp_height(src);
+    if (h < 0) return h;
+    if (dst.c != 3) return VACV_ERR_INVALID_ARG;
+    if (!roi_frames_ok(src, dst, src_index)) return VACV_ERR_INVALID_ARG;
+    if ((st = rois_options(flags, border_mode))) return st;
+    bool planar;  // decoded frames are u8 NHWC
+    const NormSpec own{};  // roi_output's and roi_fill's "normalized fp32"; its values are never used
+    if ((st = roi_output(dst, VACV_INT8, &own, planar))) return st;
+    YuvWarpRoisStdLaunch L{};
+    L.src = src.data;
+    L.src_img = src.batch;
+    L.src_row = src.row;
+    L.src_bytes = src.row * (src.h - 1) + src.w;
+    roi_fill(L, src, dst, src_index, planar, &own);
+    roi_fill_warp(L, src, m, flags, border_mode, bv);
+    L.w = src.w;
+    L.h = h;
+    L.v_first = v_first;
+    L.rgb = rgb;
+    L.mean_out = mean_out;
+    L.stddev_out = stddev_out;
+    if (!yuv_warp_rois_std_fits(L)) return VACV_ERR_UNSUPPORTED;
+    if (mean_out && mean_out == stddev_out) return VACV_ERR_INVALID_ARG;  // one array for both
+    return hip_status(launch_yuv_warp_rois_std(L, s));
+}
+
+// vacv_cvt_color_crop_resize_rois_standardize: yuv_crop_resize_rois_impl's
+// checks in its order; then the work shape's own limits (a ROI in one
+// workgroup's LDS); then the output arrays.  mean_out / stddev_out are device
+// arrays: never read or written here.
+int yuv_crop_resize_rois_std_impl(const vacv_image* src_d, const vacv_image* dst_d, int code, const int32_t* rects,
+                                  const int32_t* src_index, int interpolation, int mode, float* mean_out,
+                                  float* stddev_out, hipStream_t s) {
+    Img src, dst;
+    int st = load2(src_d, dst_d, src, dst);
+    if (st) return st;
+    if (!rects) return VACV_ERR_INVALID_ARG;
+    int v_first, rgb;
+    if ((st = color_code(code, v_first, rgb))) return st;
+    if (src.dtype != VACV_INT8 || src.c != 1 || src.layout != VACV_NHWC) return VACV_ERR_INVALID_ARG;
+    const int h = yuv420sp_height(src);
+    if (h < 0) return h;
+    if (dst.c != 3) return VACV_ERR_INVALID_ARG;
+    if (!roi_frames_ok(src, dst, src_index)) return VACV_ERR_INVALID_ARG;
+    if (interpolation != VACV_INTER_LINEAR) return VACV_ERR_UNSUPPORTED;
+    if (mode < VACV_LINEAR_REFERENCE || mode > VACV_LINEAR_OPENCV) return VACV_ERR_INVALID_ARG;
+    bool planar;  // decoded frames are u8 NHWC
+    const NormSpec own{};  // roi_output's and roi_fill's "normalized fp32"; its values are never used
+    if ((st = roi_output(dst, VACV_INT8, &own, planar))) return st;
+    YuvCropResizeRoisStdLaunch L{};
+    L.src = src.data;
+    L.src_img = src.batch;
+    L.src_row = src.row;
+    L.src_bytes = src.row * (src.h - 1) + src.w;
+    roi_fill(L, src, dst, src_index, planar, &own);
+    L.w = src.w;
+    L.h = h;
+    L.rects = rects;
+    L.mode = mode;
+    L.v_first = v_first;
+    L.rgb = rgb;
+    L.mean_out = mean_out;
+    L.stddev_out = stddev_out;
+    if (!yuv_crop_resize_rois_std_fits(L)) return VACV_ERR_UNSUPPORTED;
+    if (mean_out && mean_out == stddev_out) return VACV_ERR_INVALID_ARG;  // one array for both
+    return hip_status(launch_yuv_crop_resize_rois_std(L, s));
+}
+
 // An operator with the fused normalize.  pass(out_kind, ns) queues the operator
 // writing dst: normalized with the given statistics, or (no statistics: those
 // of its own fp32 output, per image) raw fp32, normalized in place afterwards.
@@ -1302,6 +1384,21 @@ int vacv_cvt_color_crop_resize_rois_normalize(const vacv_image* src, const vacv_
     const int st = roi_norm_spec(src, dst, mean, stddev, true, ns);
     if (st) return st;
     return yuv_crop_resize_rois_impl(src, dst, code, rects, src_index, interpolation, mode, &ns, (hipStream_t)stream);
+}
+
+int vacv_cvt_color_crop_resize_rois_standardize(const vacv_image* src, const vacv_image* dst, int code,
+                                                const int32_t* rects, const int32_t* src_index, int interpolation,
+                                                int mode, float* mean_out, float* stddev_out, void* stream) {
+    return yuv_crop_resize_rois_std_impl(src, dst, code, rects, src_index, interpolation, mode, mean_out, stddev_out,
+                                         (hipStream_t)stream);
+}
+
+int vacv_cvt_color_warp_affine_rois_standardize(const vacv_image* src, const vacv_image* dst, int code, const float* m,
+                                                const int32_t* src_index, int flags, int border_mode,
+                                                const double border_value[4], float* mean_out, float* stddev_out,
+                                                void* stream) {
+    return yuv_warp_rois_std_impl(src, dst, code, m, src_index, flags, border_mode, border_value, mean_out, stddev_out,
+                                  (hipStream_t)stream);
 }
 
 int vacv_match_template(const vacv_image* img_d, const vacv_image* tpl_d, const vacv_image* res_d, int method,

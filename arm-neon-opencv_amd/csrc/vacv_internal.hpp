@@ -399,6 +399,25 @@ struct YuvCropResizeRoisLaunch {
 };
 bool yuv_crop_resize_rois_fits(const YuvCropResizeRoisLaunch& L);  // within the kernel's 32-bit indices
 hipError_t launch_yuv_crop_resize_rois(const YuvCropResizeRoisLaunch& L, hipStream_t s);
+// ... each standardized by its own per-channel statistics, one workgroup per
+// ROI (k_yuv_crop_resize_rois_std.hip).  fp32 output; `out` is kOutNorm and
+// `norm` is unused: the statistics are the ROI's own
+struct YuvCropResizeRoisStdLaunch : YuvCropResizeRoisLaunch {
+    float* mean_out;               // device [n_roi][3], or null: not written
+    float* stddev_out;
+};
+size_t yuv_crop_resize_rois_std_lds_bytes(int w, int h);  // a workgroup's LDS (the host refuses > 64 KiB)
+bool yuv_crop_resize_rois_std_fits(const YuvCropResizeRoisStdLaunch& L);  // that, the 32-bit source offsets and grid
+hipError_t launch_yuv_crop_resize_rois_std(const YuvCropResizeRoisStdLaunch& L, hipStream_t s);
+// The ROI warps of YuvRoisLaunch, each standardized the same way
+// (k_yuv_warp_rois_std.hip)
+struct YuvWarpRoisStdLaunch : YuvRoisLaunch {
+    float* mean_out;               // device [n_roi][3], or null: not written
+    float* stddev_out;
+};
+size_t yuv_warp_rois_std_lds_bytes(int w, int h);  // a workgroup's LDS (the host refuses > 64 KiB)
+bool yuv_warp_rois_std_fits(const YuvWarpRoisStdLaunch& L);  // that, the 32-bit source offsets and grid
+hipError_t launch_yuv_warp_rois_std(const YuvWarpRoisStdLaunch& L, hipStream_t s);
 
 struct NormLaunch {                // elementwise normalize
     PlaneGeom src;

@@ -437,8 +437,9 @@ void own_stats_out(const char* fn, std::vector<Tensor>& out, const std::vector<f
 // One launch for all crops (RoiStage); each matrix is taken from where it
 // lives.  yuv_code != 0: src is a YUV420sp frame and the crops are taken from
 // its decoded (w, h, 3) image (vacv_cvt_color_warp_affine_rois).  own: every
-// crop standardized by its own statistics (vacv_warp_affine_rois_standardize),
-// which go to own_out = {mean, stddev} (own_stats_out) when it is given.
+// crop standardized by its own statistics (vacv_warp_affine_rois_standardize,
+// or vacv_cvt_color_warp_affine_rois_standardize from a YUV frame), which go
+// to own_out = {mean, stddev} (own_stats_out) when it is given.
 void warp_rois_into(const char* fn, const Tensor& src, std::vector<Tensor>& dst, const std::vector<Tensor>& M,
                     VSize dsize, int flags, int borderMode, const VScalar& bv, const Stats* stats, int yuv_code = 0,
                     bool own = false, std::vector<Tensor>* own_out = nullptr) {
@@ -473,15 +474,21 @@ void warp_rois_into(const char* fn, const Tensor& src, std::vector<Tensor>& dst,
         if (M[i].on_device())
             detail::check_hip(fn, hipMemcpyAsync(dm + 6 * i, M[i].data, 6 * sizeof(float), hipMemcpyDeviceToDevice, s));
     const vacv_image sd = st.frame(src);
-    const size_t own_bytes = own_out ? n * src.c * sizeof(float) : 0;  // of each of the two arrays
-    const vacv_image dd = st.out(n, dsize, yuv_code ? 3 : src.c, stats || own ? FP32 : src.dtype, 2 * own_bytes);
+    const int dc = yuv_code ? 3 : src.c;  // the crops' channels
+    const size_t own_bytes = own_out ? n * dc * sizeof(float) : 0;  // of each of the two arrays
+    const vacv_image dd = st.out(n, dsize, dc, stats || own ? FP32 : src.dtype, 2 * own_bytes);
     std::vector<float> own_host(2 * own_bytes / sizeof(float));
     const double border[4] = {bv.v0, bv.v1, bv.v2, bv.v3};
     if (own) {
         float* om = own_out ? reinterpret_cast<float*>(st.tail_ptr) : nullptr;
         float* os = own_out ? reinterpret_cast<float*>(st.tail_ptr + own_bytes) : nullptr;
         // a crop past one workgroup's LDS is UNSUPPORTED: check() throws
-        detail::check(fn, vacv_warp_affine_rois_standardize(&sd, &dd, dm, nullptr, flags, borderMode, border, om, os, s));
+        if (yuv_code)
+            detail::check(fn, vacv_cvt_color_warp_affine_rois_standardize(&sd, &dd, yuv_code, dm, nullptr, flags,
+                                                                          borderMode, border, om, os, s));
+        else
+            detail::check(fn,
+                          vacv_warp_affine_rois_standardize(&sd, &dd, dm, nullptr, flags, borderMode, border, om, os, s));
         if (own_out)
             detail::check_hip(fn, hipMemcpyAsync(own_host.data(), st.tail_ptr, 2 * own_bytes, hipMemcpyDeviceToHost, s));
     } else if (yuv_code && stats)
@@ -495,7 +502,7 @@ void warp_rois_into(const char* fn, const Tensor& src, std::vector<Tensor>& dst,
     else
         detail::check(fn, vacv_warp_affine_rois(&sd, &dd, dm, nullptr, flags, borderMode, border, s));
     st.scatter(dst, dd, src);  // waits for the stream
-    if (own_out) own_stats_out(fn, *own_out, own_host, src.c, n);
+    if (own_out) own_stats_out(fn, *own_out, own_host, dc, n);
 }
 
 }  // namespace
@@ -525,6 +532,13 @@ void cvt_color_warp_affine(const Tensor& yuv, std::vector<Tensor>& dst, const st
     warp_rois_into("va_cv::cvt_color_warp_affine", yuv, dst, M, dsize, flags, borderMode, borderValue, nullptr, code);
 }
 
+void cvt_color_warp_affine_standardize(const Tensor& yuv, std::vector<Tensor>& dst, const std::vector<Tensor>& M,
+                                       int code, VSize dsize, int flags, int borderMode, const VScalar& borderValue,
+                                       std::vector<Tensor>* stats) {
+    warp_rois_into("va_cv::cvt_color_warp_affine_standardize", yuv, dst, M, dsize, flags, borderMode, borderValue,
+                   nullptr, code, true, stats);
+}
+
 void cvt_color_warp_affine_normalize(const Tensor& yuv, std::vector<Tensor>& dst, const std::vector<Tensor>& M,
                                      int code, VSize dsize, int flags, int borderMode, const VScalar& borderValue,
                                      const Tensor& mean, const Tensor& stddev) {
@@ -541,8 +555,9 @@ namespace {
 // One launch for all crops (RoiStage) of the rects, truncated as crop() does.
 // yuv_code != 0: src is a YUV420sp frame and the rects are taken from its
 // decoded (w, h, 3) image (vacv_cvt_color_crop_resize_rois).  own: every crop
-// standardized by its own statistics (vacv_crop_resize_rois_standardize), which
-// go to own_out = {mean, stddev} (own_stats_out) when it is given.
+// standardized by its own statistics (vacv_crop_resize_rois_standardize, or
+// vacv_cvt_color_crop_resize_rois_standardize from a YUV frame), which go to
+// own_out = {mean, stddev} (own_stats_out) when it is given.
 void crop_resize_into(const char* fn, const Tensor& src, std::vector<Tensor>& dst, const std::vector<VRect>& rects,
                       VSize dsize, int interpolation, const Stats* stats, int yuv_code = 0, bool own = false,
                       std::vector<Tensor>* own_out = nullptr) {
@@ -578,15 +593,20 @@ void crop_resize_into(const char* fn, const Tensor& src, std::vector<Tensor>& ds
     }
     const int32_t* dr = static_cast<const int32_t*>(st.params());
     const vacv_image sd = st.frame(src);
-    const size_t own_bytes = own_out ? n * src.c * sizeof(float) : 0;  // of each of the two arrays
-    const vacv_image dd = st.out(n, dsize, yuv_code ? 3 : src.c, stats || own ? FP32 : src.dtype, 2 * own_bytes);
+    const int dc = yuv_code ? 3 : src.c;  // the crops' channels
+    const size_t own_bytes = own_out ? n * dc * sizeof(float) : 0;  // of each of the two arrays
+    const vacv_image dd = st.out(n, dsize, dc, stats || own ? FP32 : src.dtype, 2 * own_bytes);
     std::vector<float> own_host(2 * own_bytes / sizeof(float));
     if (own) {
         float* dm = own_out ? reinterpret_cast<float*>(st.tail_ptr) : nullptr;
         float* ds = own_out ? reinterpret_cast<float*>(st.tail_ptr + own_bytes) : nullptr;
         // a crop past one workgroup's LDS is UNSUPPORTED: check() throws
-        detail::check(fn, vacv_crop_resize_rois_standardize(&sd, &dd, dr, nullptr, interpolation, VACV_LINEAR_REFERENCE,
-                                                            dm, ds, st.s));
+        if (yuv_code)
+            detail::check(fn, vacv_cvt_color_crop_resize_rois_standardize(&sd, &dd, yuv_code, dr, nullptr, interpolation,
+                                                                          VACV_LINEAR_REFERENCE, dm, ds, st.s));
+        else
+            detail::check(fn, vacv_crop_resize_rois_standardize(&sd, &dd, dr, nullptr, interpolation,
+                                                                VACV_LINEAR_REFERENCE, dm, ds, st.s));
         if (own_out)
             detail::check_hip(fn, hipMemcpyAsync(own_host.data(), st.tail_ptr, 2 * own_bytes, hipMemcpyDeviceToHost, st.s));
     } else if (yuv_code && stats)
@@ -601,7 +621,7 @@ void crop_resize_into(const char* fn, const Tensor& src, std::vector<Tensor>& ds
     else
         detail::check(fn, vacv_crop_resize_rois(&sd, &dd, dr, nullptr, interpolation, VACV_LINEAR_REFERENCE, st.s));
     st.scatter(dst, dd, src);  // waits for the stream
-    if (own_out) own_stats_out(fn, *own_out, own_host, src.c, n);
+    if (own_out) own_stats_out(fn, *own_out, own_host, dc, n);
 }
 
 }  // namespace
@@ -627,6 +647,12 @@ void crop_resize_standardize(const Tensor& src, std::vector<Tensor>& dst, const 
 void cvt_color_crop_resize(const Tensor& yuv, std::vector<Tensor>& dst, const std::vector<VRect>& rects, int code,
                            VSize dsize, int interpolation) {
     crop_resize_into("va_cv::cvt_color_crop_resize", yuv, dst, rects, dsize, interpolation, nullptr, code);
+}
+
+void cvt_color_crop_resize_standardize(const Tensor& yuv, std::vector<Tensor>& dst, const std::vector<VRect>& rects,
+                                       int code, VSize dsize, int interpolation, std::vector<Tensor>* stats) {
+    crop_resize_into("va_cv::cvt_color_crop_resize_standardize", yuv, dst, rects, dsize, interpolation, nullptr, code,
+                     true, stats);
 }
 
 void cvt_color_crop_resize_normalize(const Tensor& yuv, std::vector<Tensor>& dst, const std::vector<VRect>& rects,

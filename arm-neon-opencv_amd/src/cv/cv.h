@@ -243,6 +243,16 @@ void cvt_color_warp_affine_normalize(const vision::Tensor& yuv, std::vector<visi
                                      const VScalar& borderValue = VScalar(),
                                      const vision::Tensor& mean = vision::Tensor(),
                                      const vision::Tensor& stddev = vision::Tensor());
+/// ... each standardized by ITS OWN per-channel mean and standard deviation,
+/// ONE kernel launch and no decoded frame: dst[i] is, bit for bit, what
+/// warp_affine_standardize gives on cvt_color(yuv, code)
+/// (vacv_cvt_color_warp_affine_rois_standardize).  dsize up to 144 x 144 (a
+/// larger one throws); stats as warp_affine_standardize fills it, c = 3.
+void cvt_color_warp_affine_standardize(const vision::Tensor& yuv, std::vector<vision::Tensor>& dst,
+                                       const std::vector<vision::Tensor>& M, int code, VSize dsize,
+                                       int flags = INTER_LINEAR, int borderMode = BORDER_CONSTANT,
+                                       const VScalar& borderValue = VScalar(),
+                                       std::vector<vision::Tensor>* stats = nullptr);
 /// One frame, rects.size() upright crops, ONE kernel launch: dst[i] =
 /// resize(crop(src, rects[i]), dsize), byte for byte what crop() followed by
 /// resize() gives (taps clamped at the rect's edges; vacv_crop_resize_rois).
@@ -281,6 +291,15 @@ void cvt_color_crop_resize_normalize(const vision::Tensor& yuv, std::vector<visi
                                      int interpolation = INTER_LINEAR,
                                      const vision::Tensor& mean = vision::Tensor(),
                                      const vision::Tensor& stddev = vision::Tensor());
+/// ... each standardized by ITS OWN per-channel mean and standard deviation,
+/// ONE kernel launch and no decoded frame: dst[i] is, bit for bit, what
+/// crop_resize_standardize gives on cvt_color(yuv, code)
+/// (vacv_cvt_color_crop_resize_rois_standardize).  dsize up to 144 x 144 (a
+/// larger one throws); stats as crop_resize_standardize fills it, c = 3.
+void cvt_color_crop_resize_standardize(const vision::Tensor& yuv, std::vector<vision::Tensor>& dst,
+                                       const std::vector<vision::VRect>& rects, int code, VSize dsize,
+                                       int interpolation = INTER_LINEAR,
+                                       std::vector<vision::Tensor>* stats = nullptr);
 /// A tracker's step: one frame, windows.size() search windows, ONE kernel
 /// launch.  results[i] = match_template(crop(src, windows[i]), target i,
 /// method) and, with `peaks`, (*peaks)[i] = its minMaxIdx, byte for byte what

@@ -15,7 +15,8 @@ from ._lib import (BORDER_CONSTANT, BORDER_REFLECT, BORDER_REFLECT_101, BORDER_R
 _OPS = ("cvt_color_warp_affine_rois", "cvt_color_warp_affine_rois_normalize", "crop_resize_rois",
         "crop_resize_rois_normalize", "rects_from_boxes", "cvt_color_crop_resize_rois",
         "cvt_color_crop_resize_rois_normalize", "match_template_rois", "search_origins",
-        "cvt_color_match_template_rois", "crop_resize_rois_standardize", "warp_affine_rois_standardize")
+        "cvt_color_match_template_rois", "crop_resize_rois_standardize", "warp_affine_rois_standardize",
+        "cvt_color_crop_resize_rois_standardize", "cvt_color_warp_affine_rois_standardize")
 __all__ = ["ops", "dist", "build", "VacvError", *_OPS]
 
 

@@ -102,6 +102,8 @@ SIGNATURES = {
     "vacv_cvt_color_warp_affine_rois_normalize": ([_IMG, _IMG, _I, _P, _P, _I, _I, _DP, _FP, _FP, _P], _I),
     "vacv_cvt_color_crop_resize_rois": ([_IMG, _IMG, _I, _P, _P, _I, _I, _P], _I),
     "vacv_cvt_color_crop_resize_rois_normalize": ([_IMG, _IMG, _I, _P, _P, _I, _I, _FP, _FP, _P], _I),
+    "vacv_cvt_color_crop_resize_rois_standardize": ([_IMG, _IMG, _I, _P, _P, _I, _I, _P, _P, _P], _I),
+    "vacv_cvt_color_warp_affine_rois_standardize": ([_IMG, _IMG, _I, _P, _P, _I, _I, _DP, _P, _P, _P], _I),
     "vacv_stream_synchronize": ([_P], _I),
     "vacv_release_workspace": ([], _I),
     "vacv_match_template": ([_IMG, _IMG, _IMG, _I, _P], _I),
@@ -127,7 +129,9 @@ TUNE = {"RESIZE_DIRECT": 0, "CUBIC_DIRECT": 1, "RESIZE_INTERLEAVE": 2, "DIRECT_X
 # An added export alone does not bump it (vacv_crop_resize_rois[_normalize],
 # vacv_cvt_color_crop_resize_rois[_normalize], vacv_match_template_rois,
 # vacv_cvt_color_match_template_rois, vacv_crop_resize_rois_standardize,
-# vacv_warp_affine_rois_standardize).
+# vacv_warp_affine_rois_standardize,
+# vacv_cvt_color_crop_resize_rois_standardize,
+# vacv_cvt_color_warp_affine_rois_standardize).
 ABI_VERSION = 5
 
 _lib = None

@@ -625,6 +625,64 @@ def cvt_color_crop_resize_rois_normalize(yuv: torch.Tensor, rects, w: int, h: in
     return out
 
 
+def _own_stats(n: int, stats: bool, device):
+    """The (n, 3) mean / std tensors of a standardize-from-YUV call and their pointers (None: not written)."""
+    if not stats:
+        return None, None, None, None
+    mean = torch.empty((n, 3), dtype=torch.float32, device=device)
+    std = torch.empty((n, 3), dtype=torch.float32, device=device)
+    return mean, std, mean.data_ptr(), std.data_ptr()
+
+
+def cvt_color_crop_resize_rois_standardize(yuv: torch.Tensor, rects, w: int, h: int,
+                                           code: int = L.COLOR_YUV2BGR_NV21, src_index=None,
+                                           mode: int = LINEAR_REFERENCE, layout: int = NHWC, out=None,
+                                           stats: bool = False, stream=None):
+    """cvt_color_crop_resize_rois with each crop standardized by its OWN
+    per-channel mean and standard deviation, in one launch: fp32 (n, h, w, 3),
+    or planar (n, 3, h, w) with layout=NCHW.  Bit for bit cvt_color ->
+    crop_resize_rois_standardize, without the decoded frames; yuv, rects and
+    src_index as cvt_color_crop_resize_rois takes them; an invalid rect or
+    index gives zeros with mean and stddev 0.  stats=True: returns (out, mean,
+    std), the two (n, 3) float32 device tensors of every crop's statistics.  A
+    crop must fit one workgroup's LDS (144 x 144 does): VacvError(UNSUPPORTED)
+    otherwise."""
+    y4 = _yuv4(yuv)
+    _, rects, src_index, n = _roi_batch(_as4d(y4.unsqueeze(-1), NHWC), rects, *_RECTS, src_index)
+    if out is None:
+        out = torch.empty((n, h, w, 3) if layout == NHWC else (n, 3, h, w), dtype=torch.float32, device=yuv.device)
+    mean, std, meanp, stdp = _own_stats(n, stats, yuv.device)
+    check("vacv_cvt_color_crop_resize_rois_standardize", L.load().vacv_cvt_color_crop_resize_rois_standardize(
+        ctypes.byref(_yuv_desc(y4)), ctypes.byref(describe(out, layout)), code, rects.data_ptr(),
+        _idx_ptr(src_index), INTER_LINEAR, mode, meanp, stdp, _stream(stream)))
+    return (out, mean, std) if stats else out
+
+
+def cvt_color_warp_affine_rois_standardize(yuv: torch.Tensor, ms, w: int, h: int, code: int = L.COLOR_YUV2BGR_NV21,
+                                           src_index=None, flags: int = INTER_LINEAR,
+                                           border_mode: int = BORDER_CONSTANT, border_value=(0, 0, 0, 0),
+                                           layout: int = NHWC, out=None, stats: bool = False, stream=None):
+    """cvt_color_warp_affine_rois with each crop standardized by its OWN
+    per-channel mean and standard deviation, in one launch: fp32 (n, h, w, 3),
+    or planar (n, 3, h, w) with layout=NCHW.  Bit for bit cvt_color ->
+    warp_affine_rois_standardize, without the decoded frames; yuv, ms and
+    src_index as cvt_color_warp_affine_rois takes them; border pixels count in
+    the statistics, and an index outside the frames gives zeros with mean =
+    border_value and stddev 0.  stats=True: returns (out, mean, std), the two
+    (n, 3) float32 device tensors of every crop's statistics.  A crop must fit
+    one workgroup's LDS (144 x 144 does): VacvError(UNSUPPORTED) otherwise."""
+    y4 = _yuv4(yuv)
+    _, ms, src_index, n = _roi_batch(_as4d(y4.unsqueeze(-1), NHWC), ms, *_MS, src_index)
+    if out is None:
+        out = torch.empty((n, h, w, 3) if layout == NHWC else (n, 3, h, w), dtype=torch.float32, device=yuv.device)
+    mean, std, meanp, stdp = _own_stats(n, stats, yuv.device)
+    bv, bp = _border(border_value)
+    check("vacv_cvt_color_warp_affine_rois_standardize", L.load().vacv_cvt_color_warp_affine_rois_standardize(
+        ctypes.byref(_yuv_desc(y4)), ctypes.byref(describe(out, layout)), code, ms.data_ptr(),
+        _idx_ptr(src_index), flags, border_mode, bp, meanp, stdp, _stream(stream)))
+    return (out, mean, std) if stats else out
+
+
 # ---------------------------------------------------------------------------
 # normalize / statistics
 

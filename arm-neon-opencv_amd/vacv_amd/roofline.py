@@ -156,6 +156,15 @@ def yuv_warp_rois_bytes(w_in: int, h_in: int, w_out: int, h_out: int, ms, out_es
     return int(total)
 
 
+def yuv_warp_rois_standardize_bytes(w_in: int, h_in: int, w_out: int, h_out: int, ms, stats: bool = False,
+                                    inverse_map: bool = False) -> int:
+    """B_alg of vacv_cvt_color_warp_affine_rois_standardize: yuv_warp_rois_bytes
+    with an fp32 output -- the u8 ROI and its statistics live in LDS and cost
+    no memory traffic -- plus, with stats, the two (n, 3) fp32 arrays."""
+    n = np.asarray(ms, dtype=np.float64).reshape(-1, 6).shape[0]
+    return yuv_warp_rois_bytes(w_in, h_in, w_out, h_out, ms, 4, inverse_map) + (2 * n * 3 * 4 if stats else 0)
+
+
 def warp_rois_bytes(w_in: int, h_in: int, c: int, w_out: int, h_out: int, ms, in_esize: int = 1,
                     out_esize: int = 1, inverse_map: bool = False) -> int:
     """B_alg of vacv_warp_affine_rois: the output bytes of every ROI plus the
@@ -276,3 +285,13 @@ def yuv_crop_resize_rois_bytes(w_out: int, h_out: int, rects, out_esize: int = 1
         total += w * h
         total += 2 * (((left + w - 1) >> 1) - (left >> 1) + 1) * (((top + h - 1) >> 1) - (top >> 1) + 1)
     return int(total)
+
+
+def yuv_crop_resize_rois_standardize_bytes(w_out: int, h_out: int, rects, stats: bool = False, w_in: int = None,
+                                           h_in: int = None) -> int:
+    """B_alg of vacv_cvt_color_crop_resize_rois_standardize:
+    yuv_crop_resize_rois_bytes with an fp32 output -- the u8 ROI and its
+    statistics live in LDS and cost no memory traffic -- plus, with stats, the
+    two (n, 3) fp32 arrays."""
+    n = np.asarray(rects, dtype=np.int64).reshape(-1, 4).shape[0]
+    return yuv_crop_resize_rois_bytes(w_out, h_out, rects, 4, w_in, h_in) + (2 * n * 3 * 4 if stats else 0)

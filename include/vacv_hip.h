@@ -34,7 +34,7 @@ extern "C" {
 
 /* Bumped when a signature, an enum value or the tuning enum changes.  An
  * added export alone does not bump it (vacv_crop_resize_rois[_normalize] and
- * the two _rois_standardize functions came under 5): a caller built against the older header still gets what it asked. */
+ * the four _rois_standardize functions came under 5): a caller built against the older header still gets what it asked. */
 #define VACV_ABI_VERSION 5
 #define VACV_MAX_CHANNELS 16
 
@@ -577,6 +577,61 @@ int vacv_cvt_color_crop_resize_rois_normalize(const vacv_image* src, const vacv_
                                     const int32_t* rects, const int32_t* src_index,
                                     int interpolation, int mode,
                                     const float* mean, const float* stddev, void* stream);
+
+/* The two standardize calls straight from NV21 / NV12 frames: each ROI
+ * normalized by ITS OWN per-channel mean and standard deviation, in ONE kernel
+ * launch, without the decoded frames, the u8 crops or a statistics pass.
+ * ROI i of dst and row i of mean_out / stddev_out are bit for bit what this
+ * chain gives:
+ *   1. vacv_cvt_color(frame src_index[i], code) into a (w, h, 3) INT8 frame;
+ *   2. vacv_crop_resize_rois_standardize (rects[i], interpolation, mode), or
+ *      vacv_warp_affine_rois_standardize (m[i], flags, border_mode,
+ *      border_value), on the decoded frames.
+ * src, code: exactly as vacv_cvt_color_warp_affine_rois.
+ * dst: `dst->n` ROIs of dst->w x dst->h, c = 3, FP32, NHWC or NCHW, pitched or
+ *      dense (row, plane and batch pitch), at any 4-byte alignment.  INT8:
+ *      INVALID_ARG.
+ * rects, src_index, interpolation, mode: exactly as
+ *      vacv_cvt_color_crop_resize_rois; m, src_index, flags, border_mode,
+ *      border_value: exactly as vacv_cvt_color_warp_affine_rois.  DEVICE arrays
+ *      read by the kernel, on `stream`, at execution time.
+ * mean_out, stddev_out: DEVICE arrays [dst->n][3] float, written by the kernel;
+ *      either or both may be NULL, and a NULL array is not written.  The same
+ *      non-NULL pointer for both: INVALID_ARG.
+ * The call queues one kernel, takes no workspace, copies nothing between host
+ * and device, allocates nothing and never synchronizes, and host code never
+ * dereferences the four device arrays.  Bytes of the dst allocation outside
+ * the ROI rectangles are never written.
+ * Device-supplied values cannot fault: every source read is range-checked by
+ * the hardware against the indexed frame's Y and chroma rows.  crop_resize: an
+ * index outside [0, src->n), a width or height below 2, a negative origin or
+ * an edge past the decoded frame reads no source byte and is the chain's ROI
+ * of u8 zeros -- mean 0, stddev 0, every output +0.0.  warp_affine: an index
+ * outside [0, src->n) reads no source byte and is the chain's ROI of
+ * border_value -- mean = the u8 border value per channel, stddev 0, every
+ * output +0.0; zero-determinant and non-finite maps behave as
+ * vacv_warp_affine_rois documents.
+ * VACV_ERR_UNSUPPORTED, with nothing written and before any HIP call:
+ *  - a ROI that does not fit one workgroup's 64 KiB of LDS.  The need is
+ *      crop_resize: 256 + 16 ceil(3 w h / 16) + max(8 (w + h), 3072) bytes
+ *      warp_affine: 256 + 16 ceil(3 w h / 16) + 3072 bytes
+ *    (the formulas of the two _rois_standardize calls at c = 3): 144 x 144 is
+ *    exactly 64 KiB; 112 x 112 and 128 x 128 fit;
+ *  - a frame (Y and chroma rows) of 2 GiB or more;
+ *  - dst->n > 4,194,303 (a workgroup of 1,024 threads per ROI).
+ * Order of the checks: those of vacv_cvt_color_crop_resize_rois /
+ * vacv_cvt_color_warp_affine_rois, in their order -- descriptors, rects / m,
+ * the code, the source's dtype / channels / layout, the YUV420sp shape, dst's
+ * channels, the src_index rule, interpolation then mode / flags and
+ * border_mode, dst's dtype -- then these limits, then mean_out == stddev_out. */
+int vacv_cvt_color_crop_resize_rois_standardize(const vacv_image* src, const vacv_image* dst, int code,
+                                    const int32_t* rects, const int32_t* src_index,
+                                    int interpolation, int mode,
+                                    float* mean_out, float* stddev_out, void* stream);
+int vacv_cvt_color_warp_affine_rois_standardize(const vacv_image* src, const vacv_image* dst, int code,
+                                    const float* m, const int32_t* src_index, int flags, int border_mode,
+                                    const double border_value[4],
+                                    float* mean_out, float* stddev_out, void* stream);
 
 /* ---- template matching ------------------------------------------------ */
 

@@ -29,11 +29,13 @@ def main():
                     help="--op warp_rois: time each one-call case against the same crops as a loop of single "
                          "calls (vacv_warp_affine; vacv_warp_affine_normalize + one vacv_change_layout), alternating "
                          "(the standardize case: against warp_affine_rois + normalize(NULL, NULL) + change_layout); "
-                         "--op yuv_rois: against vacv_cvt_color of all frames + vacv_warp_affine_rois[_normalize]; "
+                         "--op yuv_rois: against vacv_cvt_color of all frames + vacv_warp_affine_rois[_normalize] "
+                         "(the standardize case: + vacv_warp_affine_rois_standardize); "
                          "--op crop_resize_rois: against a loop of vacv_crop + vacv_resize[_normalize] single calls "
                          "(the standardize case: against crop_resize_rois + normalize(NULL, NULL) + change_layout); "
                          "--op yuv_crop_resize_rois: against vacv_cvt_color of all frames + "
-                         "vacv_crop_resize_rois[_normalize]; "
+                         "vacv_crop_resize_rois[_normalize] (the standardize case: + "
+                         "vacv_crop_resize_rois_standardize); "
                          "--op yuv_match_rois: against vacv_cvt_color of all frames + vacv_match_template_rois")
     ap.add_argument("--baseline-lib", default="",
                     help="--compare: libvacv_hip.so of another build (e.g. the parent commit's) to run the loop on; "
@@ -286,6 +288,23 @@ def main():
             lambda yuv7=yuv7, dms7=dms7, o7=o7: ops.cvt_color_warp_affine_rois(yuv7, dms7, 140, 210, out=o7),
             yuv_warp_rois_bytes(1280, 720, 140, 210, ms7), 64 * 140 * 210)
         chains["yuv_rois_720p_64x140x210_u8"] = dict(yuv=yuv7, ms=dms7, idx=None, out=torch.empty_like(o7), norm=False)
+        # the 1080p maps, each crop standardized by its own statistics
+        # (vacv_cvt_color_warp_affine_rois_standardize); the comparator is the
+        # chain it replaces: cvt_color of all frames, then the BGR standardize
+        # call, into preallocated buffers
+        from vacv_amd.roofline import yuv_warp_rois_standardize_bytes
+        os_ = torch.empty((256, 3, 112, 112), dtype=torch.float32, device=dev)
+        bgr, oc = torch.empty((8, 1080, 1920, 3), dtype=torch.uint8, device=dev), torch.empty_like(os_)
+
+        def warp_std_chain(yuv=yuv, dms=dms, didx=didx, bgr=bgr, oc=oc):
+            ops.cvt_color(yuv, out=bgr)
+            ops.warp_affine_rois_standardize(bgr, dms, 112, 112, src_index=didx, layout=vacv_amd.NCHW, out=oc)
+
+        cases["yuv_rois_standardize_1080p_256x112_chw"] = (
+            lambda yuv=yuv, dms=dms, didx=didx, os_=os_: ops.cvt_color_warp_affine_rois_standardize(
+                yuv, dms, 112, 112, src_index=didx, layout=vacv_amd.NCHW, out=os_),
+            yuv_warp_rois_standardize_bytes(1920, 1080, 112, 112, ms), 256 * 112 * 112)
+        std_chains["yuv_rois_standardize_1080p_256x112_chw"] = dict(frames=8, out=oc, chain=warp_std_chain)
     crop_loops = {}
     if a.op in ("crop_resize_rois", "all"):
         # many upright crops, each with its own rect, in ONE launch
@@ -382,6 +401,23 @@ def main():
             yuv_crop_resize_rois_bytes(140, 210, rects7, 1, 1280, 720), 64 * 140 * 210)
         crop_chains["yuv_crop_resize_rois_720p_64x140x210_u8"] = dict(yuv=yuv7, rects=drects7, idx=None,
                                                                       out=torch.empty_like(o7), norm=False)
+        # the same boxes, each crop standardized by its own statistics
+        # (vacv_cvt_color_crop_resize_rois_standardize); the comparator is the
+        # chain it replaces: cvt_color of all frames, then the BGR standardize
+        # call, into preallocated buffers
+        from vacv_amd.roofline import yuv_crop_resize_rois_standardize_bytes
+        os_ = torch.empty((256, 3, 112, 112), dtype=torch.float32, device=dev)
+        bgr, oc = torch.empty((8, 1080, 1920, 3), dtype=torch.uint8, device=dev), torch.empty_like(os_)
+
+        def crop_std_chain(yuv=yuv, drects=drects, didx=didx, bgr=bgr, oc=oc):
+            ops.cvt_color(yuv, out=bgr)
+            ops.crop_resize_rois_standardize(bgr, drects, 112, 112, src_index=didx, layout=vacv_amd.NCHW, out=oc)
+
+        cases["yuv_crop_resize_rois_standardize_1080p_256x112_chw"] = (
+            lambda yuv=yuv, drects=drects, didx=didx, os_=os_: ops.cvt_color_crop_resize_rois_standardize(
+                yuv, drects, 112, 112, src_index=didx, layout=vacv_amd.NCHW, out=os_),
+            yuv_crop_resize_rois_standardize_bytes(112, 112, rects, False, 1920, 1080), 256 * 112 * 112)
+        std_chains["yuv_crop_resize_rois_standardize_1080p_256x112_chw"] = dict(frames=8, out=oc, chain=crop_std_chain)
     match_loops = {}
     if a.op in ("match_rois", "all"):
         # a tracker's step (vacv_match_template_rois): 256 objects on 8 frames,
@@ -435,6 +471,7 @@ def main():
     if a.compare and a.op == "yuv_crop_resize_rois":
         compare_with_crop_chains({k: v for k, v in cases.items() if k in crop_chains}, crop_chains, a.baseline_lib,
                                  a.iters)
+        compare_with_std_chains({k: v for k, v in cases.items() if k in std_chains}, std_chains, a.iters)
         return
     if a.compare and a.op == "crop_resize_rois":
         compare_with_crop_loops({k: v for k, v in cases.items() if k in crop_loops}, crop_loops, a.iters)
@@ -442,6 +479,7 @@ def main():
         return
     if a.compare and a.op == "yuv_rois":
         compare_with_chains({k: v for k, v in cases.items() if k in chains}, chains, a.baseline_lib, a.iters)
+        compare_with_std_chains({k: v for k, v in cases.items() if k in std_chains}, std_chains, a.iters)
         return
     if a.compare:
         compare_with_loops({k: v for k, v in cases.items() if k in loops}, loops, a.baseline_lib, a.iters)
@@ -799,7 +837,9 @@ def compare_with_crop_loops(cases, loops, iters):
 
 def compare_with_std_chains(cases, chains, iters):
     """--op crop_resize_rois and --op warp_rois, the standardize cases: the one
-    call against the chain it replaces on this build -- ops.crop_resize_rois or
+    call against the chain it replaces on this build (--op yuv_rois and --op
+    yuv_crop_resize_rois: ops.cvt_color of all frames, then the BGR standardize
+    call, the case's own "chain") -- ops.crop_resize_rois or
     ops.warp_affine_rois (the chain's "u8" stage) into a u8 batch,
     ops.normalize(None, None) (the per-image statistics and the normalize) into
     an fp32 NHWC batch, ops.change_layout into the NCHW output, every buffer
@@ -822,15 +862,19 @@ def compare_with_std_chains(cases, chains, iters):
 
     for name, (fn, nbytes, px) in cases.items():
         ch = chains[name]
-        first, out = ch["u8"], ch["out"]
+        out = ch["out"]
         n, c, ho, wo = out.shape
-        u = torch.empty((n, ho, wo, c), dtype=torch.uint8, device=out.device)
-        f32 = torch.empty((n, ho, wo, c), dtype=torch.float32, device=out.device)
+        if "chain" in ch:  # the YUV cases: cvt_color + the BGR standardize call, writing `out`
+            chain = ch["chain"]
+        else:
+            first = ch["u8"]
+            u = torch.empty((n, ho, wo, c), dtype=torch.uint8, device=out.device)
+            f32 = torch.empty((n, ho, wo, c), dtype=torch.float32, device=out.device)
 
-        def chain():
-            first(u)
-            ops.normalize(u, None, None, out=f32)
-            ops.change_layout(f32, vacv_amd.NCHW, out=out)
+            def chain(first=first, u=u, f32=f32, out=out):
+                first(u)
+                ops.normalize(u, None, None, out=f32)
+                ops.change_layout(f32, vacv_amd.NCHW, out=out)
 
         for _ in range(20):
             chain()
