@@ -585,6 +585,29 @@ int warp_rois_impl(const vacv_image* src_d, const vacv_image* dst_d, const float
     return hip_status(launch_warp_rois(L, s));
 }
 
+// vacv_warp_perspective_rois[_normalize]: warp_rois_impl's contract and order
+// of checks, line for line; h is a device array [n][9] in m's place.
+int warp_persp_rois_impl(const vacv_image* src_d, const vacv_image* dst_d, const float* h, const int32_t* src_index,
+                         int flags, int border_mode, const double bv[4], const NormSpec* ns, hipStream_t s) {
+    Img src, dst;
+    int st = load2(src_d, dst_d, src, dst);
+    if (st) return st;
+    if (!h) return VACV_ERR_INVALID_ARG;
+    if (src.c != dst.c) return VACV_ERR_INVALID_ARG;
+    if (!roi_frames_ok(src, dst, src_index)) return VACV_ERR_INVALID_ARG;
+    if ((st = roi_source(src))) return st;
+    if ((st = rois_options(flags, border_mode))) return st;
+    if (!two_taps(src)) return VACV_ERR_INVALID_ARG;
+    bool planar;
+    if ((st = roi_output(dst, src.dtype, ns, planar))) return st;
+    WarpPerspRoisLaunch L{};
+    L.src = geom(src);
+    if (L.src.plane_bytes > kMaxPlaneBytes) return VACV_ERR_UNSUPPORTED;
+    roi_fill(L, src, dst, src_index, planar, ns);
+    roi_fill_warp(L, src, h, flags, border_mode, bv);
+    return hip_status(launch_warp_persp_rois(L, s));
+}
+
 // vacv_warp_affine_rois_standardize: warp_rois_impl's checks in its order, with
 // the INT8-only rule after roi_source's; then the work shape's own limits (a
 // ROI in one workgroup's LDS); then the output arrays.  mean_out / stddev_out
@@ -1155,6 +1178,68 @@ int vacv_warp_affine_rois_normalize(const vacv_image* src, const vacv_image* dst
     const int st = roi_norm_spec(src, dst, mean, stddev, false, ns);
     if (st) return st;
     return warp_rois_impl(src, dst, m, src_index, flags, border_mode, border_value, &ns, (hipStream_t)stream);
+}
+
+int vacv_warp_perspective_rois(const vacv_image* src, const vacv_image* dst, const float* h, const int32_t* src_index,
+                               int flags, int border_mode, const double border_value[4], void* stream) {
+    return warp_persp_rois_impl(src, dst, h, src_index, flags, border_mode, border_value, nullptr, (hipStream_t)stream);
+}
+
+int vacv_warp_perspective_rois_normalize(const vacv_image* src, const vacv_image* dst, const float* h,
+                                         const int32_t* src_index, int flags, int border_mode,
+                                         const double border_value[4], const float* mean, const float* stddev,
+                                         void* stream) {
+    NormSpec ns;
+    const int st = roi_norm_spec(src, dst, mean, stddev, false, ns);
+    if (st) return st;
+    return warp_persp_rois_impl(src, dst, h, src_index, flags, border_mode, border_value, &ns, (hipStream_t)stream);
+}
+
+int vacv_invert_homography(const float h[9], double inv[9]) {
+    if (!h || !inv) return VACV_ERR_INVALID_ARG;
+    invert_homography_value(h, inv);  // vacv_semantics.hpp: the kernel's own function
+    return VACV_OK;
+}
+
+// cv::getPerspectiveTransform: the 8 x 8 system of the four correspondences
+// (h8 = 1) by Gaussian elimination with partial pivoting, in double
+int vacv_perspective_transform(const float sq[8], const float dq[8], float h[9]) {
+    if (!sq || !dq || !h) return VACV_ERR_INVALID_ARG;
+    double A[8][9];
+    double scale = 0;
+    for (int i = 0; i < 4; ++i) {
+        const double x = sq[2 * i], y = sq[2 * i + 1], X = dq[2 * i], Y = dq[2 * i + 1];
+        const double r0[9] = {x, y, 1, 0, 0, 0, -x * X, -y * X, X};
+        const double r1[9] = {0, 0, 0, x, y, 1, -x * Y, -y * Y, Y};
+        for (int k = 0; k < 9; ++k) {
+            A[i][k] = r0[k];
+            A[i + 4][k] = r1[k];
+            if (!std::isfinite(r0[k]) || !std::isfinite(r1[k])) return VACV_ERR_INVALID_ARG;
+            if (k < 8) scale = std::max(scale, std::max(std::fabs(r0[k]), std::fabs(r1[k])));
+        }
+    }
+    for (int c = 0; c < 8; ++c) {
+        int p = c;
+        for (int r = c + 1; r < 8; ++r)
+            if (std::fabs(A[r][c]) > std::fabs(A[p][c])) p = r;
+        // no pivot: three of the four points of a quad are collinear (relative to the system's size)
+        if (!(std::fabs(A[p][c]) > 1e-10 * scale)) return VACV_ERR_INVALID_ARG;
+        if (p != c)
+            for (int k = 0; k < 9; ++k) std::swap(A[p][k], A[c][k]);
+        for (int r = c + 1; r < 8; ++r) {
+            const double f = A[r][c] / A[c][c];
+            for (int k = c; k < 9; ++k) A[r][k] -= f * A[c][k];
+        }
+    }
+    double x[8];
+    for (int c = 7; c >= 0; --c) {
+        double v = A[c][8];
+        for (int k = c + 1; k < 8; ++k) v -= A[c][k] * x[k];
+        x[c] = v / A[c][c];
+    }
+    for (int k = 0; k < 8; ++k) h[k] = (float)x[k];
+    h[8] = 1.f;
+    return VACV_OK;
 }
 
 int vacv_warp_affine_rois_standardize(const vacv_image* src, const vacv_image* dst, const float* m,

@@ -216,6 +216,23 @@ struct WarpRoisLaunch {
 };
 hipError_t launch_warp_rois(const WarpRoisLaunch& L, hipStream_t s);
 hipError_t launch_invert_affine(const float* m, float* inv, int n, hipStream_t s);
+// Many projective crops in one launch (k_warp_persp_rois.hip): ROI i = warp of
+// frame src_index[i] under the 3x3 homography h[i]; the fields are
+// WarpRoisLaunch's, with h in m's place
+struct WarpPerspRoisLaunch {
+    PlaneGeom src;               // NHWC frames (planes = 1)
+    PlaneGeom dst;               // ROI 0; img_pitch between ROIs; planar: plane_pitch between channel planes
+    int n_src, n_roi;
+    const float* m;              // device [n_roi][9], row-major
+    const int32_t* src_index;    // device [n_roi], or null: frame 0 (n_src == 1) or frame i
+    int inverse_map;             // m[i] is already the dst -> src map
+    float border[4];
+    int border_mode;             // kBorder* but TRANSPARENT
+    int out;                     // kOutSame or kOutNorm
+    int planar;                  // fp32 NCHW destination
+    NormSpec norm;
+};
+hipError_t launch_warp_persp_rois(const WarpPerspRoisLaunch& L, hipStream_t s);
 // ... each standardized by its own per-channel statistics, one workgroup per
 // ROI (k_warp_rois_std.hip).  u8 frames, fp32 output; `out` is kOutNorm and
 // `norm` is unused: the statistics are the ROI's own

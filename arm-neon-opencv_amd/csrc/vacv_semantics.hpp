@@ -147,6 +147,43 @@ VACV_HD void invert_affine_value(const float m[6], float inv[6]) {
     for (int k = 0; k < 6; ++k) inv[k] = a[k];
 }
 
+// The inverse of a 3x3 homography h (row-major, (x, y, 1) -> (X, Y, W)) up to
+// scale, as cv::warpPerspective inverts: the floats widened to double, the
+// adjugate (each cofactor two products and one subtraction), the determinant
+// along the first row, an IEEE double reciprocal (0 for a zero determinant:
+// the inverse is then all zeros, as invert_affine_value's); every operation
+// separately rounded.  One body for the host entry point and the kernel.
+VACV_HD void invert_homography_value(const float h[9], double inv[9]) {
+    double a[9], c[9];
+    for (int k = 0; k < 9; ++k) a[k] = (double)h[k];
+    c[0] = a[4] * a[8] - a[5] * a[7];
+    c[1] = a[2] * a[7] - a[1] * a[8];
+    c[2] = a[1] * a[5] - a[2] * a[4];
+    c[3] = a[5] * a[6] - a[3] * a[8];
+    c[4] = a[0] * a[8] - a[2] * a[6];
+    c[5] = a[2] * a[3] - a[0] * a[5];
+    c[6] = a[3] * a[7] - a[4] * a[6];
+    c[7] = a[1] * a[6] - a[0] * a[7];
+    c[8] = a[0] * a[4] - a[1] * a[3];
+    const double det = (a[0] * c[0] + a[1] * c[3]) + a[2] * c[6];
+    const double D = det != 0 ? 1. / det : 0;
+    for (int k = 0; k < 9; ++k) inv[k] = c[k] * D;
+}
+
+// Source coordinates of output pixel (x, y) under the dst -> src homography N:
+// double throughout, ONE IEEE reciprocal of the third row, the two products
+// rounded to float (cv::warpPerspective's own order).  A zero third row is not
+// special: it gives +-inf or NaN, which fail affine_tap like any far-away point.
+VACV_HD void perspective_coords(const double N[9], int x, int y, float& fx, float& fy) {
+    const double xd = (double)x, yd = (double)y;
+    const double X = (N[0] * xd + N[1] * yd) + N[2];
+    const double Y = (N[3] * xd + N[4] * yd) + N[5];
+    const double Wd = (N[6] * xd + N[7] * yd) + N[8];
+    const double r = 1.0 / Wd;
+    fx = (float)(X * r);
+    fy = (float)(Y * r);
+}
+
 // Border modes for warp_affine beyond BORDER_CONSTANT.  The reference hands
 // every other mode to OpenCV (warp_affine.cpp:114-118 -> :48-50, recursing
 // forever without it); here they extend the reference's own naive sampler:

@@ -548,6 +548,81 @@ void cvt_color_warp_affine_normalize(const Tensor& yuv, std::vector<Tensor>& dst
     warp_rois_into(fn, yuv, dst, M, dsize, flags, borderMode, borderValue, &stats, code);
 }
 
+// ---- one frame, many projective crops (vacv_warp_perspective_rois) ---------
+
+namespace {
+
+// warp_rois_into with 3x3 homographies: one launch for all crops (RoiStage),
+// each matrix taken from where it lives
+void warp_persp_rois_into(const char* fn, const Tensor& src, std::vector<Tensor>& dst, const std::vector<Tensor>& M,
+                          VSize dsize, int flags, int borderMode, const VScalar& bv, const Stats* stats) {
+    if (src.empty()) fail(fn, "empty input tensor");
+    if (src.dtype != INT8 && src.dtype != FP32) fail(fn, "warp_perspective takes INT8 or FP32");
+    if (src.layout != NHWC) fail(fn, "the crops of one frame take an NHWC frame");
+    if ((flags & ~(INTER_MAX | WARP_INVERSE_MAP)) || (flags & INTER_MAX) != INTER_LINEAR)
+        fail(fn, "only INTER_LINEAR (optionally | WARP_INVERSE_MAP) is supported for the crops of one frame");
+    if (borderMode < BORDER_CONSTANT || borderMode >= BORDER_TRANSPARENT) fail(fn, "unsupported border mode");
+    if (dsize.w < 1 || dsize.h < 1) fail(fn, "dsize must be positive");
+    if (M.empty()) fail(fn, "empty matrix list");
+    const size_t n = M.size();
+    if (n > 0x7FFFFFFFu) fail(fn, "too many matrices");
+    RoiStage st(fn, src);
+    for (const Tensor& m : M) {
+        if (m.dtype != FP32 || m.size() != 9) fail(fn, "every M must be a 3x3 FP32 tensor");
+        if (m.on_device() && m.device() != st.lease.device()) fail(fn, "operands live on different devices");
+    }
+    if (src.on_device() && src.device() != st.lease.device()) fail(fn, "operands live on different devices");
+    const hipStream_t s = st.s;
+    float* mp = static_cast<float*>(st.host_params(9, n, "out of memory staging the matrices"));
+    std::memset(mp, 0, n * 9 * sizeof(float));
+    for (size_t i = 0; i < n; ++i)
+        if (!M[i].on_device()) std::memcpy(mp + 9 * i, M[i].data, 9 * sizeof(float));
+    float* dm = static_cast<float*>(st.params());
+    for (size_t i = 0; i < n; ++i)  // over the zeros of its place
+        if (M[i].on_device())
+            detail::check_hip(fn, hipMemcpyAsync(dm + 9 * i, M[i].data, 9 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    const vacv_image sd = st.frame(src);
+    const vacv_image dd = st.out(n, dsize, src.c, stats ? FP32 : src.dtype);
+    const double border[4] = {bv.v0, bv.v1, bv.v2, bv.v3};
+    if (stats)
+        detail::check(fn, vacv_warp_perspective_rois_normalize(&sd, &dd, dm, nullptr, flags, borderMode, border,
+                                                               stats->m(), stats->s(), s));
+    else
+        detail::check(fn, vacv_warp_perspective_rois(&sd, &dd, dm, nullptr, flags, borderMode, border, s));
+    st.scatter(dst, dd, src);  // waits for the stream
+}
+
+}  // namespace
+
+void warp_perspective(const Tensor& src, std::vector<Tensor>& dst, const std::vector<Tensor>& M, VSize dsize, int flags,
+                      int borderMode, const VScalar& borderValue) {
+    warp_persp_rois_into("va_cv::warp_perspective", src, dst, M, dsize, flags, borderMode, borderValue, nullptr);
+}
+
+void warp_perspective_normalize(const Tensor& src, std::vector<Tensor>& dst, const std::vector<Tensor>& M, VSize dsize,
+                                int flags, int borderMode, const VScalar& borderValue, const Tensor& mean,
+                                const Tensor& stddev) {
+    static const char* fn = "va_cv::warp_perspective_normalize";
+    const Stats stats = read_stats(fn, mean, stddev, src.c, false);
+    if (!stats.m()) fail(fn, "the crops of one frame need mean and stddev (no per-image statistics)");
+    warp_persp_rois_into(fn, src, dst, M, dsize, flags, borderMode, borderValue, &stats);
+}
+
+void warp_perspective(const Tensor& src, Tensor& dst, const Tensor& M, VSize dsize, int flags, int borderMode,
+                      const VScalar& borderValue) {
+    std::vector<Tensor> one;
+    warp_persp_rois_into("va_cv::warp_perspective", src, one, std::vector<Tensor>(1, M), dsize, flags, borderMode,
+                         borderValue, nullptr);
+    dst = one[0];
+}
+
+void get_perspective_transform(const float src_quad[8], const float dst_quad[8], Tensor& M) {
+    static const char* fn = "va_cv::get_perspective_transform";
+    M.create(3, 3, FP32);
+    if (!M.data) fail(fn, "out of memory creating the matrix");
+    detail::check(fn, vacv_perspective_transform(src_quad, dst_quad, static_cast<float*>(M.data)));
+}
+
 // ---- one frame, many upright crops (vacv_crop_resize_rois) -----------------
 
 namespace {

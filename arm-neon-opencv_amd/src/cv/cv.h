@@ -253,6 +253,30 @@ void cvt_color_warp_affine_standardize(const vision::Tensor& yuv, std::vector<vi
                                        int flags = INTER_LINEAR, int borderMode = BORDER_CONSTANT,
                                        const VScalar& borderValue = VScalar(),
                                        std::vector<vision::Tensor>* stats = nullptr);
+/// One frame, M.size() projective crops, ONE kernel launch (the rectified
+/// quads of an OCR, plate or document pipeline): dst[i] = OpenCV's
+/// warpPerspective shape under the 3x3 homography M[i] (3x3x1 FP32 tensor,
+/// row-major; FORWARD maps, or dst -> src maps with flags | WARP_INVERSE_MAP),
+/// the coordinates in double with one reciprocal and the pixel the naive
+/// warp_affine sampler's (vacv_warp_perspective_rois).  Everything else --
+/// src, flags, border modes, staging, placement of dst -- as the warp_affine
+/// overload with a vector of matrices above.
+void warp_perspective(const vision::Tensor& src, std::vector<vision::Tensor>& dst,
+                      const std::vector<vision::Tensor>& M, VSize dsize, int flags = INTER_LINEAR,
+                      int borderMode = BORDER_CONSTANT, const VScalar& borderValue = VScalar());
+/// The same with the fused normalize (FP32 crops); mean and stddev are required.
+void warp_perspective_normalize(const vision::Tensor& src, std::vector<vision::Tensor>& dst,
+                                const std::vector<vision::Tensor>& M, VSize dsize, int flags = INTER_LINEAR,
+                                int borderMode = BORDER_CONSTANT, const VScalar& borderValue = VScalar(),
+                                const vision::Tensor& mean = vision::Tensor(),
+                                const vision::Tensor& stddev = vision::Tensor());
+/// OpenCV's single-image signature: a batch of one.
+void warp_perspective(const vision::Tensor& src, vision::Tensor& dst, const vision::Tensor& M, VSize dsize,
+                      int flags = INTER_LINEAR, int borderMode = BORDER_CONSTANT,
+                      const VScalar& borderValue = VScalar());
+/// cv::getPerspectiveTransform: M (3x3x1 host FP32, M[8] = 1) maps the four
+/// points src_quad (x0 y0 .. x3 y3) to dst_quad.  A degenerate quad throws.
+void get_perspective_transform(const float src_quad[8], const float dst_quad[8], vision::Tensor& M);
 /// One frame, rects.size() upright crops, ONE kernel launch: dst[i] =
 /// resize(crop(src, rects[i]), dsize), byte for byte what crop() followed by
 /// resize() gives (taps clamped at the rect's edges; vacv_crop_resize_rois).

@@ -16,7 +16,8 @@ _OPS = ("cvt_color_warp_affine_rois", "cvt_color_warp_affine_rois_normalize", "c
         "crop_resize_rois_normalize", "rects_from_boxes", "cvt_color_crop_resize_rois",
         "cvt_color_crop_resize_rois_normalize", "match_template_rois", "search_origins",
         "cvt_color_match_template_rois", "crop_resize_rois_standardize", "warp_affine_rois_standardize",
-        "cvt_color_crop_resize_rois_standardize", "cvt_color_warp_affine_rois_standardize")
+        "cvt_color_crop_resize_rois_standardize", "cvt_color_warp_affine_rois_standardize",
+        "warp_perspective_rois", "warp_perspective_rois_normalize", "homographies_from_quads")
 __all__ = ["ops", "dist", "build", "VacvError", *_OPS]
 
 

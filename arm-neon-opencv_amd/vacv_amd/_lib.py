@@ -92,6 +92,10 @@ SIGNATURES = {
     "vacv_warp_affine_rois_normalize": ([_IMG, _IMG, _P, _P, _I, _I, _DP, _FP, _FP, _P], _I),
     "vacv_warp_affine_rois_standardize": ([_IMG, _IMG, _P, _P, _I, _I, _DP, _P, _P, _P], _I),
     "vacv_invert_affine_device": ([_P, _P, _I, _P], _I),
+    "vacv_warp_perspective_rois": ([_IMG, _IMG, _P, _P, _I, _I, _DP, _P], _I),
+    "vacv_warp_perspective_rois_normalize": ([_IMG, _IMG, _P, _P, _I, _I, _DP, _FP, _FP, _P], _I),
+    "vacv_invert_homography": ([_FP, _DP], _I),
+    "vacv_perspective_transform": ([_FP, _FP, _FP], _I),
     "vacv_crop_resize_rois": ([_IMG, _IMG, _P, _P, _I, _I, _P], _I),
     "vacv_crop_resize_rois_normalize": ([_IMG, _IMG, _P, _P, _I, _I, _FP, _FP, _P], _I),
     "vacv_crop_resize_rois_standardize": ([_IMG, _IMG, _P, _P, _I, _I, _P, _P, _P], _I),
@@ -131,7 +135,9 @@ TUNE = {"RESIZE_DIRECT": 0, "CUBIC_DIRECT": 1, "RESIZE_INTERLEAVE": 2, "DIRECT_X
 # vacv_cvt_color_match_template_rois, vacv_crop_resize_rois_standardize,
 # vacv_warp_affine_rois_standardize,
 # vacv_cvt_color_crop_resize_rois_standardize,
-# vacv_cvt_color_warp_affine_rois_standardize).
+# vacv_cvt_color_warp_affine_rois_standardize,
+# vacv_warp_perspective_rois[_normalize], vacv_invert_homography,
+# vacv_perspective_transform).
 ABI_VERSION = 5
 
 _lib = None

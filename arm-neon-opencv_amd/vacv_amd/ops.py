@@ -379,6 +379,98 @@ def invert_affine_device(ms: torch.Tensor, out=None, stream=None) -> torch.Tenso
     return out
 
 
+_HS = ("hs", torch.float32,
+       lambda a: (a.dim() == 2 and a.shape[1] == 9) or (a.dim() == 3 and tuple(a.shape[1:]) == (3, 3)),
+       "(n, 9) or (n, 3, 3)", "hs holds no matrix")
+
+
+def warp_perspective_rois(src: torch.Tensor, hs, w: int, h: int, src_index=None, flags: int = INTER_LINEAR,
+                          border_mode: int = BORDER_CONSTANT, border_value=(0, 0, 0, 0), out=None,
+                          stream=None) -> torch.Tensor:
+    """Many projective crops in one launch: out[i] = warp_perspective(src[src_index[i]], hs[i], w, h).
+    src and src_index as warp_affine_rois takes them.  hs: (n, 9) or (n, 3, 3)
+    float32 device tensor of homographies, forward maps, or dst -> src maps with
+    flags | WARP_INVERSE_MAP (homographies_from_quads makes those).  Read by the
+    kernel when it runs on `stream`, not by this call.  Returns (n, h, w, c)."""
+    s4, hs, src_index, n = _roi_batch(_as4d(src, NHWC), hs, *_HS, src_index)
+    if out is None:
+        out = torch.empty((n, h, w, s4.shape[3]), dtype=src.dtype, device=src.device)
+    bv, bp = _border(border_value)
+    check("vacv_warp_perspective_rois", L.load().vacv_warp_perspective_rois(
+        ctypes.byref(describe(s4, NHWC)), ctypes.byref(describe(out, NHWC)), hs.data_ptr(),
+        _idx_ptr(src_index), flags, border_mode, bp, _stream(stream)))
+    return out
+
+
+def warp_perspective_rois_normalize(src: torch.Tensor, hs, w: int, h: int, mean, std, src_index=None,
+                                    out_layout: int = NHWC, flags: int = INTER_LINEAR,
+                                    border_mode: int = BORDER_CONSTANT, border_value=(0, 0, 0, 0), out=None,
+                                    stream=None) -> torch.Tensor:
+    """warp_perspective_rois with the fused normalize: fp32 (n, h, w, c), or
+    planar (n, c, h, w) with out_layout=NCHW (c = 3 or 1), the model-input layout."""
+    s4, hs, src_index, n = _roi_batch(_as4d(src, NHWC), hs, *_HS, src_index)
+    c = s4.shape[3]
+    if mean is None or std is None:
+        raise ValueError("warp_perspective_rois_normalize needs mean and stddev (no per-image statistics for ROIs)")
+    if out is None:
+        out = torch.empty((n, h, w, c) if out_layout == NHWC else (n, c, h, w), dtype=torch.float32,
+                          device=src.device)
+    bv, bp = _border(border_value)
+    (ma, meanp), (sa, stdp) = _meanstd(mean, std, c)
+    check("vacv_warp_perspective_rois_normalize", L.load().vacv_warp_perspective_rois_normalize(
+        ctypes.byref(describe(s4, NHWC)), ctypes.byref(describe(out, out_layout)), hs.data_ptr(),
+        _idx_ptr(src_index), flags, border_mode, bp, meanp, stdp, _stream(stream)))
+    return out
+
+
+def invert_homography(h) -> np.ndarray:
+    """The float64 inverse (up to scale) of a float32 3x3 homography: what the
+    ROI kernel samples through for a forward map.  Host; returns (9,) float64."""
+    hh, hp = _fptr(np.asarray(h, np.float32).reshape(9))
+    inv = np.zeros(9, np.float64)
+    check("vacv_invert_homography",
+          L.load().vacv_invert_homography(hp, inv.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
+    return inv
+
+
+def perspective_transform(src_quad, dst_quad) -> np.ndarray:
+    """cv::getPerspectiveTransform: the (9,) float32 homography (h8 = 1) that
+    maps the four points src_quad (4, 2) to dst_quad.  Host; a degenerate quad
+    raises VacvError(INVALID_ARG)."""
+    sq, sp = _fptr(np.asarray(src_quad, np.float32).reshape(8))
+    dq, dp = _fptr(np.asarray(dst_quad, np.float32).reshape(8))
+    out = np.zeros(9, np.float32)
+    check("vacv_perspective_transform",
+          L.load().vacv_perspective_transform(sp, dp, out.ctypes.data_as(ctypes.POINTER(ctypes.c_float))))
+    return out
+
+
+def homographies_from_quads(quads: torch.Tensor, w: int, h: int) -> torch.Tensor:
+    """(n, 4, 2) quads (TL, TR, BR, BL, in frame pixels) -> (n, 9) float32
+    dst -> src maps for warp_perspective_rois(..., flags | WARP_INVERSE_MAP):
+    the output corners (0, 0), (w-1, 0), (w-1, h-1), (0, h-1) land on the
+    quad's points.  The closed-form square-to-quad map, elementwise in float64
+    on the quads' device: no solver, no host round trip."""
+    if w < 2 or h < 2:
+        raise ValueError(f"homographies_from_quads needs w, h >= 2, got {w} x {h}")
+    if quads.dim() != 3 or tuple(quads.shape[1:]) != (4, 2):
+        raise ValueError(f"quads must have shape (n, 4, 2), got {tuple(quads.shape)}")
+    q = quads.to(torch.float64)
+    x0, y0, x1, y1 = q[:, 0, 0], q[:, 0, 1], q[:, 1, 0], q[:, 1, 1]
+    x2, y2, x3, y3 = q[:, 2, 0], q[:, 2, 1], q[:, 3, 0], q[:, 3, 1]
+    dx1, dy1, dx2, dy2 = x1 - x2, y1 - y2, x3 - x2, y3 - y2
+    sx, sy = x0 - x1 + x2 - x3, y0 - y1 + y2 - y3
+    den = dx1 * dy2 - dx2 * dy1
+    g = (sx * dy2 - dx2 * sy) / den
+    k = (dx1 * sy - sx * dy1) / den
+    # the unit square's map (u, v, 1) -> (a u + b v + x0, d u + e v + y0, g u + k v + 1), u = x / (w-1), v = y / (h-1)
+    su, sv = 1.0 / (w - 1), 1.0 / (h - 1)
+    rows = [(x1 - x0 + g * x1) * su, (x3 - x0 + k * x3) * sv, x0,
+            (y1 - y0 + g * y1) * su, (y3 - y0 + k * y3) * sv, y0,
+            g * su, k * sv, torch.ones_like(g)]
+    return torch.stack(rows, dim=1).to(torch.float32).contiguous()
+
+
 def rects_from_boxes(boxes: torch.Tensor) -> torch.Tensor:
     """(n, 4) float32 boxes (left, top, right, bottom) -> (n, 4) int32 rects
     (left, top, width, height) as crop_naive truncates them (crop.cpp:128-131):

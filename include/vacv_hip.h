@@ -381,6 +381,48 @@ int vacv_warp_affine_rois_standardize(const vacv_image* src, const vacv_image* d
  * DEVICE out, queued on `stream`. */
 int vacv_invert_affine_device(const float* m, float* inv, int n, void* stream);
 
+/* Many projective crops in one launch: the rectified quadrilaterals of an OCR,
+ * plate or document pipeline, each with its own 3x3 map (no counterpart in the
+ * reference; OpenCV's warpPerspective shape).
+ * dst image i = warp_perspective of src image src_index[i] under h[i].
+ * h: DEVICE array [dst->n][9] float, row-major h0..h8, (x, y, 1) -> (X, Y, W).
+ *    Forward maps, or dst -> src maps with flags | VACV_WARP_INVERSE_MAP.
+ * Everything else -- src, dst, src_index, flags, border_mode, border_value, the
+ * order of the checks, what is UNSUPPORTED, and that nothing is copied,
+ * allocated or synchronized -- is vacv_warp_affine_rois', with h in m's place.
+ * Pixel (x, y) of ROI i: N = vacv_invert_homography(h[i]), or (double)h[i]
+ * under VACV_WARP_INVERSE_MAP; in double, each operation rounded separately,
+ *   X = (N0*x + N1*y) + N2, Y = (N3*x + N4*y) + N5, W = (N6*x + N7*y) + N8,
+ *   r = 1 / W, fx = (float)(X*r), fy = (float)(Y*r)
+ * (cv::warpPerspective's coordinates); from (fx, fy) on the pixel is
+ * vacv_warp_affine_rois' -- byte for byte the single pixel of a 1 x 1
+ * vacv_warp_affine_rois ROI of the same frame under the map [1 0 fx; 0 1 fy]
+ * with VACV_WARP_INVERSE_MAP, the same border mode and value.
+ * Device-supplied values cannot fault: an index outside [0, src->n) gives a
+ * ROI of border_value in every border mode and reads no source byte; a
+ * singular forward map inverts to all zeros; W == 0 or non-finite values give
+ * +-inf or NaN coordinates, which are border pixels like any far-away point;
+ * every sampler read is range-checked against the indexed frame by the
+ * hardware. */
+int vacv_warp_perspective_rois(const vacv_image* src, const vacv_image* dst, const float* h,
+                               const int32_t* src_index, int flags, int border_mode,
+                               const double border_value[4], void* stream);
+/* The same, normalized: dst, mean and stddev as vacv_warp_affine_rois_normalize
+ * takes them (FP32, NHWC or NCHW for c = 3 and c = 1). */
+int vacv_warp_perspective_rois_normalize(const vacv_image* src, const vacv_image* dst, const float* h,
+                                         const int32_t* src_index, int flags, int border_mode,
+                                         const double border_value[4],
+                                         const float* mean, const float* stddev, void* stream);
+/* The inverse of a homography up to scale, in double: the floats widened, the
+ * adjugate (each cofactor p*q - r*s), det = (h0*c0 + h1*c3) + h2*c6, times
+ * 1 / det (all zeros for det == 0).  The kernel's own function.  Host only. */
+int vacv_invert_homography(const float h[9], double inv_out[9]);
+/* cv::getPerspectiveTransform: the homography (h8 = 1) that maps the four
+ * points src_quad (x0 y0 .. x3 y3) to dst_quad, solved in double with partial
+ * pivoting and stored as floats.  A degenerate quad (three collinear points):
+ * VACV_ERR_INVALID_ARG.  Host only. */
+int vacv_perspective_transform(const float src_quad[8], const float dst_quad[8], float h_out[9]);
+
 /* Many upright crops in one launch: the reference's crop(src, box) followed
  * by resize(crop, dsize) per detected box (Crop::crop_naive, crop.cpp:128-142,
  * then ResizeNaive::resize_naive_inter_linear_u8 / _fp32), without the crops

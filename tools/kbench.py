@@ -460,8 +460,64 @@ def main():
             256 * 33 * 33)
         match_chains["yuv_match_rois_1080p_256x64x64_t32_ccoeff_normed"] = dict(
             yuv=yuv, tpls=tpls, origins=dorg, idx=didx, w=64, h=64, method=method)
+    persp_pairs = {}
+    if a.op in ("warp_persp_rois", "all"):
+        # many small projective crops in ONE launch (vacv_warp_perspective_rois):
+        # the warp_rois geometry -- boxes rotated by +-30 degrees, ~250 px per
+        # side, centres anywhere in the frame -- with every corner moved by up to
+        # 15 % of the side.  The yardstick is vacv_warp_affine_rois[_normalize]
+        # on the same boxes without the corner jitter: the neighbouring kernel,
+        # the same sampling with cheaper coordinates (orientation only).
+        import numpy as np
+        rng = np.random.default_rng(20261021)
+
+        def boxes(n, fw, fh, wo, ho, foot=250.0):
+            quads, ms = np.zeros((n, 4, 2), np.float32), np.zeros((n, 6), np.float32)
+            for i in range(n):
+                ang, s = np.deg2rad(rng.uniform(-30.0, 30.0)), max(wo, ho) / foot
+                cx, cy = rng.uniform(0, fw), rng.uniform(0, fh)
+                ca, sa = np.cos(ang) / s, np.sin(ang) / s  # dst -> src: rotate, scale, centre on (cx, cy)
+                inv = np.array([[ca, -sa, cx - ca * wo / 2 + sa * ho / 2], [sa, ca, cy - sa * wo / 2 - ca * ho / 2]])
+                ms[i] = inv.reshape(6)
+                corners = np.array([[0, 0, 1], [wo - 1, 0, 1], [wo - 1, ho - 1, 1], [0, ho - 1, 1]], np.float64)
+                quads[i] = corners @ inv.T + rng.uniform(-0.15, 0.15, (4, 2)) * foot
+            return quads, ms
+
+        inv_flag = vacv_amd.INTER_LINEAR | vacv_amd.WARP_INVERSE_MAP
+        src = frames(8, 1080, 1920)
+        quads, ms = boxes(256, 1920, 1080, 112, 112)
+        dhs = ops.homographies_from_quads(torch.from_numpy(quads).to(dev), 112, 112)
+        dms = torch.from_numpy(ms).to(dev)
+        didx = torch.from_numpy(np.arange(256, dtype=np.int32) % 8).to(dev)
+        o, oa = (torch.empty((256, 112, 112, 3), dtype=torch.uint8, device=dev) for _ in range(2))
+        nb = 256 * 112 * 112 * 3 * 2  # output bytes + as many source bytes (a crop's footprint is ~5x its pixels; cached)
+        cases["warp_persp_rois_1080p_256x112_u8"] = (
+            lambda: ops.warp_perspective_rois(src, dhs, 112, 112, src_index=didx, flags=inv_flag, out=o), nb, 256 * 112 * 112)
+        persp_pairs["warp_persp_rois_1080p_256x112_u8"] = (
+            lambda: ops.warp_affine_rois(src, dms, 112, 112, src_index=didx, flags=inv_flag, out=oa))
+        of, ofa = (torch.empty((256, 3, 112, 112), dtype=torch.float32, device=dev) for _ in range(2))
+        cases["warp_persp_rois_normalize_1080p_256x112_chw"] = (
+            lambda: ops.warp_perspective_rois_normalize(src, dhs, 112, 112, MEAN, STD, src_index=didx,
+                                                        out_layout=vacv_amd.NCHW, flags=inv_flag, out=of),
+            256 * 112 * 112 * 3 * 5, 256 * 112 * 112)
+        persp_pairs["warp_persp_rois_normalize_1080p_256x112_chw"] = (
+            lambda: ops.warp_affine_rois_normalize(src, dms, 112, 112, MEAN, STD, src_index=didx,
+                                                   out_layout=vacv_amd.NCHW, flags=inv_flag, out=ofa))
+        src7 = frames(1, 720, 1280)
+        quads7, ms7 = boxes(64, 1280, 720, 140, 210)
+        dhs7 = ops.homographies_from_quads(torch.from_numpy(quads7).to(dev), 140, 210)
+        dms7 = torch.from_numpy(ms7).to(dev)
+        o7, o7a = (torch.empty((64, 210, 140, 3), dtype=torch.uint8, device=dev) for _ in range(2))
+        cases["warp_persp_rois_720p_64x140x210_u8"] = (
+            lambda: ops.warp_perspective_rois(src7, dhs7, 140, 210, flags=inv_flag, out=o7), 64 * 140 * 210 * 3 * 2,
+            64 * 140 * 210)
+        persp_pairs["warp_persp_rois_720p_64x140x210_u8"] = (
+            lambda: ops.warp_affine_rois(src7, dms7, 140, 210, flags=inv_flag, out=o7a))
     if a.only:
         cases = {k: v for k, v in cases.items() if a.only in k}
+    if a.compare and a.op == "warp_persp_rois":
+        compare_persp_with_affine({k: v for k, v in cases.items() if k in persp_pairs}, persp_pairs, a.iters)
+        return
     if a.compare and a.op == "yuv_match_rois":
         compare_with_match_chains({k: v for k, v in cases.items() if k in match_chains}, match_chains, a.iters)
         return
@@ -497,6 +553,58 @@ def main():
             ops.set_tuning(k, int(v))
         tag = " ".join(f"{k}={v}" for k, v in combo)
         run_cases(cases, a.iters, tag)
+
+
+def compare_persp_with_affine(cases, pairs, iters):
+    """--op warp_persp_rois: vacv_warp_perspective_rois[_normalize] against
+    vacv_warp_affine_rois[_normalize] on the same boxes without the corner
+    jitter, on this build: alternating, medians, end to end (host clock around
+    a synchronised stream) and between HIP events.  The affine call computes
+    OTHER crops (no projective part): the ratio says what the fp64 coordinates
+    cost next to the float ones, nothing about correctness."""
+    import time
+
+    import torch
+
+    def timed(f):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        f()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    def event_ms(f):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s = torch.cuda.current_stream()
+        e0.record(s)
+        f()
+        e1.record(s)
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1)
+
+    def med(v):
+        return sorted(v)[len(v) // 2]
+
+    for name, (fn, nbytes, px) in cases.items():
+        aff = pairs[name]
+        for _ in range(100):  # clocks ramp before the first timed call
+            aff()
+            fn()
+        torch.cuda.synchronize()
+        t_p, t_a, e_p, e_a = [], [], [], []
+        for _ in range(iters):
+            t_a.append(timed(aff))
+            t_p.append(timed(fn))
+            e_a.append(event_ms(aff))
+            e_p.append(event_ms(fn))
+        print(json.dumps({"case": name, "pixels": int(px), "iters": iters,
+                          "persp_ms_median": round(med(t_p), 4), "persp_ms_min": round(min(t_p), 4),
+                          "affine_ms_median": round(med(t_a), 4), "affine_ms_min": round(min(t_a), 4),
+                          "persp_over_affine": round(med(t_p) / med(t_a), 3),
+                          "persp_events_ms_median": round(med(e_p), 4), "affine_events_ms_median": round(med(e_a), 4),
+                          "persp_over_affine_events": round(med(e_p) / med(e_a), 3),
+                          "persp_Gpx_per_s_events": round(px / med(e_p) / 1e6, 2),
+                          "clock": "host, stream synchronised; HIP events on the stream"}), flush=True)
 
 
 def compare_with_loops(cases, loops, baseline_lib, iters):
